@@ -9,6 +9,14 @@ per-agent deviation partials are all-reduced over RCCL every round, which is the
 exchange step.  ``value`` = rounds/s in units of the 1024 x 2^20 workload, summed over ranks.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c2-mix|c3|c4]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds what the
+headline figure does not need: the CPU baselines (every workload), and on the c2 line the
+measured HBM copy / triad ceilings, the second measurement with per-edge FDLA weights and, at
+N > 1, the agent-partition child probes.  ``--dump-outputs DIR`` (c2, c2-mix) writes what the
+last timed round left -- the agents' rows (a fixed seeded column sample when large), dev_sq and
+dev_max -- as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
 
 Other BASELINE configs (not the headline line; run on request):
   c3  ANNModel MLP consensus SGD, 256 agents x 164,560 params, B=64 synthetic MNIST-shaped
@@ -88,7 +96,16 @@ def parse():
     p.add_argument("--params", type=int, default=1 << 20)
     p.add_argument("--cpu-cols", type=int, default=1 << 18,
                    help="columns of the bounded CPU-baseline sample (all agents)")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true",
+                   help="--full without the CPU baseline")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: CPU baselines, and "
+                        "on the c2 line the HBM copy / triad ceilings, the FDLA-weights probe "
+                        "and (N>1) the agent-partition child probes")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="c2 / c2-mix: after the timed steps write what the last one computed "
+                        "(X rows or a seeded column sample of them, dev_sq, dev_max) as "
+                        "DIR/<name>.npy, float32")
     p.add_argument("--trace", action="store_true",
                    help="c2-gossip: traced passes (Mixer.mix(times, eps) stop test every round)")
     p.add_argument("--no-graph", action="store_true", help="c3/c5: eager launches, no hipGraph")
@@ -109,19 +126,56 @@ def parse():
                         "solver per shape: 6.90 vs 6.66 steps/s; --no-cudnn-benchmark keeps the "
                         "default heuristic)")
     p.add_argument("--no-halo-probe", action="store_true",
-                   help="N>1: skip the c4 agent-partition (RCCL halo exchange) probe that the "
-                        "c2 line carries as its 'c4_halo' object")
+                   help="--full at N>1 without the c4 agent-partition (RCCL halo exchange) "
+                        "probe that the c2 line carries as its 'c4_halo' object")
     p.add_argument("--weights", default="best-constant", choices=["best-constant", "fdla"],
                    help="c2/c2-mix: mixing weights of the headline loop (fdla: the committed "
                         "per-edge FDLA SDP weights of the c2 graph, tests/golden/fdla_rr4_1024.npz)")
     p.add_argument("--no-fdla-probe", action="store_true",
-                   help="c2 at N=1: skip the second measurement with per-edge FDLA weights")
+                   help="c2 --full at N=1 without the second measurement with per-edge FDLA "
+                        "weights")
     p.add_argument("--halo-overlap", default="both", choices=["both", "whole", "chunks", "split"],
                    help="c4 at N>1: halo overlap scheme(s) to time (sharding.HaloShard; both = "
                         "all three)")
     p.add_argument("--dist-backend", default="nccl",
                    help="nccl (= RCCL, default) or gloo (multi-rank rehearsal on one GPU)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ("c2", "c2-mix"):
+        p.error("--dump-outputs is implemented for the c2 and c2-mix workloads")
+    if not args.full:   # a plain run: the timed steps and their line only
+        args.no_cpu = args.no_fdla_probe = args.no_halo_probe = True
+    return args
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # of X; dev_sq and dev_max are a few KB (64 MB in all at most)
+
+
+def dump_columns(n, P):
+    """The columns of an n x P matrix that --dump-outputs keeps: None (all) within the budget,
+    else a sorted sample drawn with a fixed seed."""
+    k = max(1, DUMP_BUDGET_BYTES // (4 * n))
+    if k >= P:
+        return None
+    return np.sort(np.random.default_rng(20240).choice(P, size=k, replace=False))
+
+
+def dump_outputs(path, eng, dev_sq):
+    """--dump-outputs: what a caller of the timed path holds after the last timed round, as
+    float32 .npy files -- X.npy: the agents' rows in agent order (all columns when they fit the
+    budget, else a sorted sample of columns drawn with a fixed seed, the same for every run of
+    the same shape); dev_sq.npy: ||x_a - mean||^2 per agent (all-reduced at N > 1); dev_max.npy:
+    max_a ||x_a - mean||."""
+    os.makedirs(path, exist_ok=True)
+    R = eng.rows()
+    cols = dump_columns(eng.n, eng.P)
+    if cols is not None:
+        R = R.index_select(1, torch.as_tensor(cols, device=R.device))
+    np.save(os.path.join(path, "X.npy"), R.float().cpu().numpy())
+    np.save(os.path.join(path, "dev_sq.npy"), dev_sq.float().cpu().numpy())
+    np.save(os.path.join(path, "dev_max.npy"),
+            torch.sqrt(dev_sq.max()).float().reshape(1).cpu().numpy())
 
 
 def log(*a):
@@ -1810,6 +1864,8 @@ def main():
     value = n_gpus * args.steps / elapsed                 # 1024 x 2^20-equivalent rounds / s
     achieved = bytes_per_round / (launch_ms / 1e3) / 1e9  # GB/s of the fused round launch
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, dev_sq_global if pending else eng.agent_dev_sq())
     fdla = None
     if rank == 0 and world == 1 and sgd and args.weights == "best-constant" and \
             not args.no_fdla_probe:
@@ -1819,7 +1875,9 @@ def main():
     if rank == 0:
         kname = kernel_name(plan, sgd, True, n)
         traffic, traffic_src = traffic_from_profile(kname)
-        ceiling, triad, ceiling_variants = copy_ceiling(dev)
+        ceiling = triad = ceiling_variants = None
+        if args.full:   # 4 GiB streams through dl_stream_copy: runs of their own
+            ceiling, triad, ceiling_variants = copy_ceiling(dev)
         cpu = None
         if not args.no_cpu and world == 1:   # the CPU baseline is an N=1 figure
             cb = cpu_baseline(csr, n, P, min(args.cpu_cols, P), sgd, lr)
@@ -1858,7 +1916,7 @@ def main():
                          "bytes_per_launch": bytes_per_round, "launch_ms": launch_ms,
                          "measured_copy_ceiling_GBs": ceiling,
                          "measured_triad_ceiling_GBs": triad,
-                         "frac_of_measured_triad": achieved / triad,
+                         "frac_of_measured_triad": achieved / triad if triad else None,
                          "stream_variants_GBs": ceiling_variants,
                          **rocprof_fields(kname, bytes_per_round)},
             "cpu_baseline": cpu,

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Same-box interleaved runs of one bench line under several environment settings:
 #   scripts/env_matrix.sh <out_dir> <reps> "<name>:<VAR=val,VAR=val or ->" ... -- <bench args...>
+# (--full among the bench args for the triad fraction echoed beside each value.)
 # Each run under its own time limit; trouble ends the script.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/$1; REPS=$2; shift 2

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 TAG=${1:-pmc}; shift
-ARGS=${@:-"--steps 10 --warmup 2 --no-cpu"}
+ARGS=${@:-"--full --steps 10 --warmup 2 --no-cpu"}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 i=0

@@ -7,7 +7,7 @@ TAG=${1:-r01}
 shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-ARGS=${@:-"--steps 20 --warmup 3 --no-cpu"}
+ARGS=${@:-"--full --steps 20 --warmup 3 --no-cpu"}
 run() {
     local name=$1; shift
     echo "=== $name"

@@ -8,7 +8,7 @@ TAG=$1; shift
 LINES=${@:-"c2 c3 c4 c4rank c4ba c4gather"}
 for l in $LINES; do
     case $l in
-        c2) A="--steps 20 --warmup 3 --no-cpu --no-fdla-probe" ;;
+        c2) A="--full --steps 20 --warmup 3 --no-cpu --no-fdla-probe" ;;   # --full: the triad kernels
         c3) A="--workload c3 --steps 50 --warmup 5 --no-cpu" ;;
         c4) A="--workload c4 --steps 20 --warmup 3 --no-cpu" ;;
         c4rank) A="--workload c4-rank --steps 30 --warmup 3 --no-cpu" ;;

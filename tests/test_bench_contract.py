@@ -54,6 +54,31 @@ def test_driver_command_line_parses(bench, monkeypatch):
     assert p.c3_layout == "tiled" and p.c3_tile_cols == 32
 
 
+def test_plain_run_leaves_the_extras_to_full(bench, monkeypatch):
+    """A plain run times its steps and nothing else: the CPU baselines, the FDLA-weights probe and
+    the N > 1 child probes are --full's (--no-cpu and its kin still subtract from --full), and
+    --dump-outputs names a directory for the headline path's outputs only."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    p = bench.parse()
+    assert not p.full and p.no_cpu and p.no_fdla_probe and p.no_halo_probe
+    assert p.steps == 7 and p.warmup == 2 and p.dump_outputs is None
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    p = bench.parse()
+    assert p.full and not (p.no_cpu or p.no_fdla_probe or p.no_halo_probe)
+    assert p.dump_outputs == "out"
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--no-cpu"])
+    p = bench.parse()
+    assert p.full and p.no_cpu and not p.no_fdla_probe
+    for argv in (["--workload", "c3", "--dump-outputs", "out"], ["--steps", "0"]):
+        monkeypatch.setattr("sys.argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse()
+    # the whole dump stays within 64 MB: X's sample plus dev_sq and dev_max
+    cols = bench.dump_columns(1024, 1 << 20)
+    assert 1024 * len(cols) * 4 + 1024 * 4 + 4 <= 64 * 10 ** 6
+    assert bench.dump_columns(64, 4096) is None
+
+
 def test_halo_probe_failure_carries_child_stderr(bench):
     """A failing child run (here: 2 gloo ranks of bench --workload c4 on a host with no GPU, which
     die in torch.cuda.set_device) comes back with its traceback tail in the record, so a failed

@@ -257,7 +257,7 @@ def test_full_size_round_column_slices(cuda):
 def test_full_size_round_fdla_weights(cuda):
     """BASELINE config c2 at full size with the mixing weights north_star names: the per-edge
     FDLA weights of the c2 graph from utils/fast_averaging.py's SDP (the committed
-    tests/golden/fdla_rr4_1024.npz, the weights bench.py's fdla_probe times every run; W = I -
+    tests/golden/fdla_rr4_1024.npz, the weights bench.py --full's fdla_probe times; W = I -
     L(w), every row its own weights: shared_row_weights 0, all n(d + 1) weights staged).  Fused
     local step + mix + deviation over 1024 agents x 2^20 params in the column-tiled layout:
     column slices bit-exact against oracle/cref, the fused deviation within 1e-5 of the oracle's.
