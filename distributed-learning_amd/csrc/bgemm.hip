@@ -84,10 +84,11 @@ __device__ __forceinline__ float xent_row(float v, int lane, int classes, int la
 }
 
 // Block tile BM x BN = (16 TM WM) x (16 TN WN): the 4 waves form a WM x WN grid and each owns
-// TM x TN MFMA 16x16 tiles.  Shapes used (launch_bgemm): 64 x 160 (WM 4, TN 10) for the
-// batch-row GEMMs -- one workgroup per agent covers a 150-wide layer with 6 % padding instead of
-// 28 % -- 160 x 64 (TM 10, WN 4) for the weight gradients (all 150 rows of dW in one tile, so
-// each input slice is read once), and 64 x 64 (2 x 2 waves of 2 x 2) for the cross-entropy head.
+// TM x TN MFMA 16x16 tiles.  Every GEMM and the cross-entropy head use 64 x 64 (2 x 2 waves of
+// 2 x 2) by default.  The other instantiations (launch_t) are measurement alternatives behind
+// DLAMD_BGEMM_SHAPE: 64 x 160 (WM 4, TN 10; one workgroup covers a 150-wide layer with 6 %
+// padding instead of 28 %) and 160 x 64 (TM 10, WN 4; all 150 rows of dW in one tile) measured
+// 20-30 % slower on c3, the 32- and 16-row tiles within 5 % (profiles/HISTORY.md).
 template <bool TA, bool TB, int WM, int TM, int WN, int TN, bool XENT>
 __global__ void __launch_bounds__(256) bgemm_kernel(BgemmArgs p) {
     static_assert(WM * WN == 4, "4 waves");
@@ -254,16 +255,12 @@ __global__ void __launch_bounds__(256) xent_grad_kernel(const float *__restrict_
 //   0: 64 x 64  (2x2 waves of 2x2)    1: 32 x 64 (2x1, 2x2)    2: 32 x 32 (2x1, 2x1)
 //   3: 64 x 160 (4x1, 1x10)           4: 160 x 64 (1x10, 4x1)  5: 16 x 64 (1x1, 4x1)
 // The cross-entropy head always uses shape 0.  DLAMD_BGEMM_SHAPE=<rows<=64>,<rows>64>
-// overrides the defaults (a measurement knob).
+// overrides the defaults (a measurement knob, read on every call like the other DLAMD_* knobs).
 int bgemm_shape(const BgemmArgs &p) {
-    static int small = -1, large = -1;
-    if (small < 0) {
-        small = 0;
-        large = 0;
-        if (const char *v = getenv("DLAMD_BGEMM_SHAPE")) {
-            if (v[0] >= '0' && v[0] <= '5') small = v[0] - '0';
-            if (v[1] == ',' && v[2] >= '0' && v[2] <= '5') large = v[2] - '0';
-        }
+    int small = 0, large = 0;
+    if (const char *v = getenv("DLAMD_BGEMM_SHAPE")) {
+        if (v[0] >= '0' && v[0] <= '5') small = v[0] - '0';
+        if (v[1] == ',' && v[2] >= '0' && v[2] <= '5') large = v[2] - '0';
     }
     return p.M <= 64 ? small : large;
 }

@@ -1636,6 +1636,12 @@ int dl_bgemm(const dl_bgemm_args *a, dl_stream_t stream) {
     if (a->epi == DL_EPI_BIAS_XENT && (a->M > 64 || a->N > 64 || !a->labels))
         return fail(DL_ERR_INVALID, "dl_bgemm: cross-entropy epilogue needs M <= 64 rows, "
                                     "N <= 64 classes and labels");
+    // output batches must not overlap: two workgroups would write the same floats (input
+    // strides may be 0, a shared operand)
+    if (a->batch > 1 && (a->sC < (int64_t)(a->M - 1) * a->ldc + a->N ||
+                         (a->rowsum && a->s_rowsum < a->M)))
+        return fail(DL_ERR_INVALID, "dl_bgemm: output batch stride smaller than one batch "
+                                    "(sC >= (M-1)*ldc + N, s_rowsum >= M)");
     dl::BgemmArgs p{};
     p.batch = a->batch; p.M = a->M; p.N = a->N; p.K = a->K;
     p.A = a->A; p.lda = a->lda; p.sA = a->sA; p.ta = a->ta;
@@ -1655,6 +1661,9 @@ int dl_xent_grad(const float *Z, int64_t sZ, const int32_t *y, int64_t sY, float
     if (!Z || !y || !dZ || batch <= 0 || batch > 65535 || rows <= 0 || classes <= 0 ||
         classes > 64)
         return fail(DL_ERR_INVALID, "dl_xent_grad: bad arguments");
+    if (batch > 1 && sD < (int64_t)rows * classes)
+        return fail(DL_ERR_INVALID, "dl_xent_grad: output batch stride sD smaller than one batch "
+                                    "(rows * classes)");
     hipError_t e = dl::launch_xent_grad(Z, sZ, y, sY, dZ, sD, loss, batch, rows, classes,
                                         static_cast<hipStream_t>(stream));
     return e == hipSuccess ? DL_OK : hip_fail(e, "xent_grad launch");

@@ -544,6 +544,9 @@ int dl_async_read(const double *arena, int64_t ld, int32_t slot, int64_t n_param
  *      the torch.nn.CrossEntropyLoss head in the same launch: C[b] receives
  *      dZ = (softmax(z) - onehot(labels[b])) / M and loss[b] (nullable) the mean loss; labels
  *      must lie in [0, N).  Deterministic (fixed-order sums).
+ * Batch strides: an input stride may be 0 (one operand shared by every batch); with batch > 1
+ * the output strides must keep the batches apart, sC >= (M-1) ldc + N and s_rowsum >= M
+ * (dl_xent_grad: sD >= rows classes), otherwise DL_ERR_INVALID.
  * fp32 MFMA (16x16x4), exact fp32 products. */
 enum dl_epilogue {
     DL_EPI_NONE = 0, DL_EPI_BIAS = 1, DL_EPI_BIAS_RELU = 2, DL_EPI_BIAS_TANH = 3,

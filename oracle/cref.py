@@ -31,6 +31,9 @@ def lib():
         L.ref_sgd_step.argtypes = [P, i64, P, i64, P, i64, P, i64, i32, i64, f32, f32, f32, f32,
                                    i32, i32]
         L.ref_sgd_step.restype = None
+        L.ref_bgemm.argtypes = [i32, i32, i32, i32, P, i64, i64, i32, P, i64, i64, i32,
+                                P, i64, i64, i32, P, i64, P, i64, i64, P, P, i64]
+        L.ref_bgemm.restype = None
         _lib = L
     return _lib
 
@@ -70,6 +73,33 @@ def deviation_sq(X, mean=None):
     d = np.empty(X.shape[0], np.float64)
     lib().ref_deviation_sq(_p(X), X.shape[1], X.shape[0], X.shape[1], _p(mean), _p(d))
     return d
+
+
+def bgemm(batch, M, N, K, A, lda, sA, ta, B, ldb, sB, tb, C, ldc, sC, epi=0, bias=None, s_bias=0,
+          H=None, ldh=0, sH=0, C2=None, rowsum=None, s_rowsum=0):
+    """dl_bgemm as a k-ordered fp32 fma chain (ref_bgemm in mix_ref.c; arguments as
+    dl_bgemm_args).  A, B, bias, H and the outputs C, C2 (epi 6: the second DTANH candidate),
+    rowsum are flat contiguous fp32 arrays; the outputs are written in place, logical elements
+    only.  For epi 3, 4 and 8 C receives the pre-activation z."""
+    def span(rows, width, ld, stride):   # one past the last element addressed
+        return (batch - 1) * stride + (rows - 1) * ld + width
+    need = [(A, span(K if ta else M, M if ta else K, lda, sA)),
+            (B, span(N if tb else K, K if tb else N, ldb, sB)), (C, span(M, N, ldc, sC))]
+    if bias is not None:
+        need.append((bias, span(1, N, 0, s_bias)))
+    if 5 <= epi <= 7:
+        need.append((H, span(M, N, ldh, sH)))
+    if epi == 6:
+        need.append((C2, span(M, N, ldc, sC)))
+    if rowsum is not None:
+        need.append((rowsum, span(1, M, 0, s_rowsum)))
+    for arr, n in need:
+        if arr is None or arr.dtype != np.float32 or not arr.flags.c_contiguous or arr.size < n:
+            raise ValueError("bgemm: operands must be contiguous fp32 arrays covering their span")
+    if min(batch, M, N, K, lda, ldb, ldc, sA, sB, sC, s_bias, s_rowsum) < 0 or ldh < 0 or sH < 0:
+        raise ValueError("bgemm: negative size or stride")
+    lib().ref_bgemm(batch, M, N, K, _p(A), lda, sA, int(ta), _p(B), ldb, sB, int(tb), _p(C), ldc,
+                    sC, int(epi), _p(bias), s_bias, _p(H), ldh, sH, _p(C2), _p(rowsum), s_rowsum)
 
 
 def sgd_step(X, G, buf=None, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,

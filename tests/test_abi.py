@@ -189,6 +189,74 @@ def test_new_entry_points_validate_before_any_device_call():
     assert b"halo" in lib.dl_last_error()
 
 
+def test_bgemm_and_xent_grad_validate_before_any_device_call():
+    """dl_bgemm, dl_xent_grad: every refusal is one defect in otherwise valid arguments and comes
+    back as DL_ERR_INVALID with a message; nothing is launched (runs without a GPU).  With
+    batch > 1 the output batch strides must keep the batches apart."""
+    from distributed_learning_amd import _lib
+    lib = _lib.load()
+
+    def valid(**kw):
+        # 3 batches of a 40 x 24 x 16 product, every stride exactly one batch's extent
+        a = _lib.DlBgemmArgs(batch=3, M=40, N=24, K=16, A=1 << 20, lda=16, sA=640, ta=0,
+                             B=1 << 21, ldb=24, sB=384, tb=0, C=1 << 22, ldc=24, sC=960, epi=0)
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    def refused(a, word):
+        rc = lib.dl_bgemm(ctypes.byref(a) if a is not None else None, None)
+        assert rc == _lib.DL_ERR_INVALID
+        msg = lib.dl_last_error()
+        assert msg and word in msg, (word, msg)
+
+    refused(None, b"dl_bgemm")
+    for field in ("A", "B", "C"):
+        refused(valid(**{field: None}), b"pointers")
+    for batch in (0, 65536):
+        refused(valid(batch=batch), b"sizes")
+    for field in ("M", "N", "K"):
+        for v in (0, -1):
+            refused(valid(**{field: v}), b"sizes")
+    for epi in (-1, 9):
+        refused(valid(epi=epi), b"epilogue")
+    refused(valid(lda=15), b"leading dimension")                      # ta 0: lda >= K
+    refused(valid(ta=1, lda=39, sA=640), b"leading dimension")        # ta 1: lda >= M
+    refused(valid(ldb=23), b"leading dimension")                      # tb 0: ldb >= N
+    refused(valid(tb=1, ldb=15), b"leading dimension")                # tb 1: ldb >= K
+    refused(valid(ldc=23), b"leading dimension")
+    for epi in (5, 6, 7):
+        refused(valid(epi=epi), b"needs H")                           # H NULL
+        refused(valid(epi=epi, H=1 << 23, ldh=23, sH=960), b"ldh >= N")
+    lab = dict(epi=8, labels=1 << 24, s_labels=64)
+    refused(valid(M=65, sC=65 * 24, **lab), b"cross-entropy")
+    refused(valid(N=65, ldb=65, ldc=65, sC=40 * 65, **lab), b"cross-entropy")
+    refused(valid(epi=8), b"labels")
+    # overlapping output batches: two workgroups would write the same floats
+    extent = 39 * 24 + 24
+    for sC in (extent - 1, 24, 0, -extent):
+        refused(valid(sC=sC), b"batch stride")
+    refused(valid(ldc=31, sC=39 * 31 + 23), b"batch stride")
+    for sr in (39, 0, -40):
+        refused(valid(rowsum=1 << 25, s_rowsum=sr), b"batch stride")
+
+    def xent(Z=1 << 20, sZ=50, y=1 << 21, sY=5, dZ=1 << 22, sD=50, batch=3, rows=5, classes=10):
+        rc = lib.dl_xent_grad(Z, sZ, y, sY, dZ, sD, None, batch, rows, classes, None)
+        assert rc == _lib.DL_ERR_INVALID
+        assert lib.dl_last_error().startswith(b"dl_xent_grad")
+    xent(Z=None)
+    xent(y=None)
+    xent(dZ=None)
+    xent(batch=0)
+    xent(batch=65536)
+    xent(rows=0)
+    xent(classes=0)
+    xent(classes=65, sZ=5 * 65, sD=5 * 65)
+    for sD in (49, 0, -50):
+        xent(sD=sD)
+        assert b"sD" in lib.dl_last_error()
+
+
 def test_mix_until_validates_and_sizes():
     """dl_mix_until / dl_mix_until_fits: argument errors and the LDS fit come back as status
     codes before any launch (runs without a GPU)."""

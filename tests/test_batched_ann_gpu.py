@@ -16,7 +16,10 @@ def _flat_grads(m):
                                            (5, 64, (52, 40, 7), "fused"),
                                            (3, 64, (16, 152, 16), "fused"),
                                            (7, 33, (50, 40, 7), "auto"),
-                                           (3, 5, (20, 15, 3), "auto")])
+                                           (3, 5, (20, 15, 3), "auto"),
+                                           # batch > 64: plain bias epilogue + dl_xent_grad, and
+                                           # the > 64-row tile selector on the batch-row GEMMs
+                                           (2, 80, (20, 24, 5), "auto")])
 def test_gradients_match_autograd(cuda, n, b, dims, path):
     from distributed_learning_amd.networks import ANNModel
     from distributed_learning_amd.networks.batched_ann import BatchedANN
