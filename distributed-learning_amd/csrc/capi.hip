@@ -1,6 +1,7 @@
-// C ABI of libdlamd.so (include/dlamd.h): argument validation, kernel-configuration planning,
-// workspace carving and error reporting.  No exceptions cross this boundary; every entry point
-// returns a dl_status and leaves a thread-local message for dl_last_error().
+// C ABI of libdlamd.so (include/dlamd.h): argument validation, workspace carving, launches and
+// error reporting; the kernel configuration of a round comes from the planner (plan.h).  No
+// exceptions cross this boundary; every entry point returns a dl_status and leaves a thread-local
+// message for dl_last_error().
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -50,358 +51,33 @@ constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// Workgroups of the one-round tile kernel per resident slot on the column-tiled layout: its
-// persistent grid is oversubscribed 2x, the second half of the workgroups starting as the first ones retire.
-// Measured on MI355X (scripts/grid_sweep.py, profiles/r05/grid_sweep.log): the c2 and c4 rounds
-// stream at 5.90-5.93 TB/s with 2x against 5.28-5.41 TB/s with exactly one workgroup per CU, on
-// the same box (3x: 5.74-5.80, 4x: 5.75-5.84).  Forcing one resident workgroup per CU through
-// LDS changes nothing, so the gain is not co-residency.  Row-major operands (c3's N = 256 rows)
-// keep one slot's grid (3247 vs 3206 steps/s).  DLAMD_GRID_MULT=k (1..8) overrides it.
-int grid_mult() {
-    const char *m = getenv("DLAMD_GRID_MULT");
-    const int k = m ? atoi(m) : 2;
-    return k < 1 ? 1 : (k > 8 ? 8 : k);
-}
-
-// ... for a launch of n_tiles tiles over `slots` resident workgroups: the 2x grid pays on long
-// persistent launches (c2 / c4: 128 tile passes per slot); on short ones (c3 column-tiled: 2572
-// tiles of 64 columns on 512 slots, 5 passes) the second wave of workgroups only adds its ramp:
-// 105.3 vs 110.1 us with one slot's grid (scripts/c3_round_probe.py, profiles/r12/c3_round).
-// An explicit DLAMD_GRID_MULT still applies everywhere.
-int grid_mult_for(int64_t n_tiles, int64_t slots) {
-    if (!getenv("DLAMD_GRID_MULT") && n_tiles < 16 * slots) return 1;
-    return grid_mult();
-}
-
-// Upper bound of per-workgroup partial rows any path writes.
 // MI355X Infinity Cache (MALL), shared by all XCDs
 constexpr size_t kMallBytes = (size_t)256 << 20;
-
-int max_parts() {
-    int p = 2 * device_cus() * grid_mult();
-    return p < 256 ? 256 : p;
-}
 
 bool overlaps(const void *a, size_t an, const void *b, size_t bn) {
     const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
     return x < y + bn && y < x + an;
 }
 
-struct Plan {
-    dl_mix_plan pub;
-    int chunks;
-    bool dev;
-    uint32_t csr_off, scratch_off;
-    int head;       // path 5: CSR entries per row in registers (the rest in LDS)
-    int tail_fmt;   // path 5: LDS tail entries of 8 B (2) or 6 B (1)
-    int grp;        // path 1, column-tiled: data tiles per kernel tile (0 / 1: one)
-};
+using dl::Plan;
+using dl::TracePlan;
 
-// Workgroups per CU the tile kernel may use (LDS permitting): 2 unless DLAMD_WG_PER_CU=1
-// (a measurement knob).
-int wg_per_cu_cap() {
-    const char *v = getenv("DLAMD_WG_PER_CU");
-    return (v && v[0] == '1') ? 1 : 2;
+// The planners of plan.h for the current device and environment; a failure's text goes to
+// dl_last_error().
+template <class P>
+int plan_with(int (*planner)(const dl_mix_args &, int, const dl::Knobs &, P *, char *),
+              const dl_mix_args *a, const dl::Knobs &k, P *pl) {
+    char err[dl::kErrLen];
+    const int rc = planner(*a, device_cus(), k, pl, err);
+    return rc ? fail(rc, "%s", err) : DL_OK;
 }
-
-// Persistent grid for n_tiles tiles and at most gmax workgroups: the fewest workgroups that
-// still finish in the same number of passes, so every workgroup walks ceil(n_tiles/gmax) or one
-// fewer tiles.  The time of a persistent HBM-bound launch is its longest workgroup's tile
-// count; with gmax workgroups and a ragged last pass (c3: 1286 tiles on 256 CUs = 6 passes for
-// an average of 5.02) the idle CUs of that pass are pure tail.  Fewer, evenly loaded workgroups
-// keep the same number of passes while each one gets a larger share of HBM.
-// DLAMD_BALANCE_GRID=0 (a measurement knob) keeps gmax.
-int64_t balanced_grid(int64_t n_tiles, int64_t gmax) {
-    if (gmax <= 0) return 1;
-    if (n_tiles <= gmax) return n_tiles;
-    const char *v = getenv("DLAMD_BALANCE_GRID");
-    if (v && v[0] == '0') return gmax;
-    const int64_t passes = (n_tiles + gmax - 1) / gmax;
-    return (n_tiles + passes - 1) / passes;
-}
-
-int next_pow2_chunks(int64_t n_params) {
-    int64_t need = (n_params + 3) / 4;
-    int c = 1;
-    while (c < dl::kMaxChunks && c < need) c <<= 1;
-    return c;
-}
-
-// LDS bytes of the register-head + LDS-tail tile kernel (path 5) for R rows at c chunks, or 0
-// when it does not apply: the nnz - head * R tail entries behind the tile and the mean scratch,
-// 8 B per entry ({weight, row} pairs, *fmt = 2) when that fits, else 6 B (weights + u16 rows,
-// *fmt = 1; the only form at a 5-entry head, whose registers leave no room for the pairs'
-// unrolled loop); the tail's u16 row map (setup only) must fit the tile area.
-int64_t reg_tail_lds(const dl_csr &W, int32_t R, int c, bool want_dev, int *head_out,
-                     int *fmt_out = nullptr) {
-    const int head = dl::reg_head_rows(W.min_row_nnz);
-    if (W.uniform_row_nnz == 5 || !dl::reg_tail_supported(c, R, head, 0)) return 0;
-    const int64_t ntail = (int64_t)W.nnz - (int64_t)head * R;
-    if (ntail < 0 || ntail > 65535) return 0;
-    const int64_t tile = (int64_t)R * c * 16;
-    const int64_t scratch = want_dev ? (int64_t)(dl::kTileThreads / 64) * c * 16 : 0;
-    if (tile > 65536 || 2 * ntail > tile) return 0;
-    for (int fmt = head < 5 ? 2 : 1; fmt >= 1; --fmt) {
-        const int64_t lds = tile + scratch + (((fmt == 2 ? 8 : 6) * ntail + 15) & ~(int64_t)15);
-        if (lds > dl::kLdsBytes) continue;
-        if (head_out) *head_out = head;
-        if (fmt_out) *fmt_out = fmt;
-        return lds;
-    }
-    return 0;
-}
-
-// DLAMD_FORCE_REG=1 (tests only): the register-CSR kernels (paths 4 / 5) wherever they apply,
-// so the reference's small fixtures pin them too
-bool force_reg_env() {
-    const char *f = getenv("DLAMD_FORCE_REG");
-    const char *g = getenv("DLAMD_FORCE_GATHER");
-    return f && f[0] == '1' && !(g && g[0] == '1');
-}
-
-// R = every source row (local + halo); halo rounds have no register-CSR kernels
-int choose_tiled_chunks(const dl_csr &W, int32_t R, uint32_t csr, bool want_dev, bool halo) {
-    if (R > 65535) return 0;
-    const bool reg_any = !halo && (dl::reg_csr_supported(1, R, W.uniform_row_nnz, 0) ||
-                                   reg_tail_lds(W, R, 1, want_dev, nullptr) > 0);
-    if (force_reg_env() && reg_any) return 1;
-    if (csr > 0) {
-        for (int c = dl::kMaxChunks; c >= 1; c >>= 1) {
-            // (the column-tiled halo kernel runs at most 4 row passes per thread)
-            if ((int64_t)R * c > (int64_t)(halo ? 4 : dl::kRowsPerThread) * dl::kTileThreads)
-                continue;
-            const int64_t tile = (int64_t)R * c * 16;
-            if (tile > 65536 && c > 1) continue;
-            const int64_t scratch = want_dev ? (int64_t)(dl::kTileThreads / 64) * c * 16 : 0;
-            if (tile + csr + scratch <= dl::kLdsBytes) return c;
-        }
-    }
-    if (halo) return 0;
-    // the CSR does not fit beside any tile: the register-CSR kernels need LDS for the tile (and
-    // path 5 for the CSR entries past each row's register head)
-    const int64_t tile = (int64_t)R * 16;
-    const int64_t scratch = want_dev ? (int64_t)(dl::kTileThreads / 64) * 16 : 0;
-    if (dl::reg_csr_supported(1, R, W.uniform_row_nnz, 0) && tile <= 65536 &&
-        tile + scratch <= dl::kLdsBytes)
-        return 1;
-    if (reg_tail_lds(W, R, 1, want_dev, nullptr) > 0) return 1;
-    return 0;
-}
-
-// Local source rows of a round: n_local_src, or n_rows when 0 (dlamd.h).
-inline int32_t local_src(const dl_mix_args *a) {
-    return a->n_local_src > 0 ? a->n_local_src : a->W.n_rows;
-}
-
-// An irregular graph of more than 2048 agents takes the register-head + LDS-tail kernel (path 5)
-// even when its whole CSR fits LDS beside the tile: above 2048 agents the tile is one 4-column
-// chunk either way, and path 1's per-lane CSR loop from LDS (row pointers, weights and rows read
-// per entry, a wave as long as its longest row) runs Barabasi-Albert m = 1 at 250 rounds/s
-// against 430 for path 5 (4096 x 2^18, `bench.py --workload c4-ba --irregular ba1`).
-bool prefer_reg_tail(const dl_csr &W, int32_t R, int c) {
-    return c == 1 && R > 2048 && W.uniform_row_nnz == 0 && dl::reg_head_rows(W.min_row_nnz) > 0;
-}
-
-// Register-CSR plan for c chunks -- path 4 (regular, 5 entries per row, all in registers) or
-// path 5 (rows of >= min_row_nnz entries: register head + LDS tail) -- or false when neither
-// applies.
-bool plan_reg(const dl_mix_args *a, int c, bool want_dev, Plan *pl) {
-    const int32_t R = a->W.n_rows;
-    if (a->n_halo > 0 || local_src(a) != R) return false;
-    const int64_t tile = (int64_t)R * c * 16;
-    const int64_t scratch = want_dev ? (int64_t)(dl::kTileThreads / 64) * c * 16 : 0;
-    int head = 0;
-    int64_t lds = 0;
-    if (dl::reg_csr_supported(c, R, a->W.uniform_row_nnz, 0)) {
-        lds = tile + scratch;
-        if (lds > dl::kLdsBytes) return false;
-    } else {
-        lds = reg_tail_lds(a->W, R, c, want_dev, &head, &pl->tail_fmt);
-        if (lds == 0) return false;
-    }
-    const int64_t T = 4 * c;
-    const int64_t n_tiles = (a->n_params + T - 1) / T;
-    if (n_tiles > 0x7fffffff) return false;
-    int bpc = (int)(dl::kLdsBytes / lds);
-    if (bpc > wg_per_cu_cap()) bpc = wg_per_cu_cap();
-    pl->pub.path = head > 0 ? 5 : 4;
-    pl->pub.tile_cols = (int32_t)T;
-    pl->pub.grid = (int32_t)balanced_grid(
-        n_tiles, (int64_t)device_cus() * bpc *
-                     (a->tile_cols > 0 ? grid_mult_for(n_tiles, (int64_t)device_cus() * bpc) : 1));
-    pl->pub.lds_bytes = (int32_t)lds;
-    pl->pub.n_tiles = (int32_t)n_tiles;
-    pl->pub.regular = head > 0 ? 0 : 1;
-    pl->pub.head = head > 0 ? head : 5;
-    pl->pub.tail_fmt = head > 0 ? pl->tail_fmt : 0;
-    pl->chunks = c;
-    pl->head = head;
-    pl->csr_off = (uint32_t)(tile + scratch);   // path 5: the LDS tail
-    pl->scratch_off = (uint32_t)tile;
-    return true;
-}
-
-// Pick the kernel configuration for a mix round.
 int plan_mix(const dl_mix_args *a, Plan *pl) {
-    std::memset(pl, 0, sizeof *pl);
-    const int32_t R = local_src(a) + a->n_halo;
-    const int32_t nnz = a->W.nnz;
-    // the halo round's column sums use the same LDS scratch as the fused deviation
-    const bool want_dev = a->dev_sq || a->dev_max || a->mean || a->colsum_out;
-    pl->dev = want_dev;
-    const int reg = a->W.uniform_row_nnz > 0 ? 1 : 0;
-    const int32_t n_w = (reg && a->W.shared_row_weights) ? a->W.uniform_row_nnz : nnz;
-    const uint32_t csr = dl::csr_lds_bytes(a->W.n_rows, nnz, reg, n_w);
-    int cmax = next_pow2_chunks(a->n_params);
-    // DLAMD_MAX_TILE_CHUNKS=c (a measurement knob) caps the row-major tile at 4c columns
-    if (const char *mc = getenv("DLAMD_MAX_TILE_CHUNKS")) {
-        const int m = atoi(mc);
-        while (m >= 1 && cmax > m) cmax >>= 1;
-    }
-    // DLAMD_FORCE_GATHER=1 (tests only) forces the general gather kernel; DLAMD_FORCE_REG=1
-    // (tests only) the register-CSR kernels (paths 4 / 5) wherever they apply, so the reference's
-    // small fixtures pin them too
-    const char *force = getenv("DLAMD_FORCE_GATHER");
-    const bool force_gather = force && force[0] == '1';
-    const bool force_reg = force_reg_env();
-    if (a->tile_cols > 0) {  // column-tiled layout: the tile width is fixed by the data
-        const int c = a->tile_cols / 4;
-        const int64_t tile = (int64_t)R * c * 16;
-        const int64_t scratch = want_dev ? (int64_t)(dl::kTileThreads / 64) * c * 16 : 0;
-        const int64_t lds = tile + csr + scratch;
-        if ((csr == 0 || lds > dl::kLdsBytes || force_reg || prefer_reg_tail(a->W, R, c)) &&
-            R <= 65535 && plan_reg(a, c, want_dev, pl))
-            return DL_OK;
-        if (csr == 0 || R > 65535 || (int64_t)R * c > (int64_t)dl::kRowsPerThread * dl::kTileThreads ||
-            (a->n_halo > 0 && (int64_t)R * c > 4 * (int64_t)dl::kTileThreads) ||
-            lds > dl::kLdsBytes)
-            return fail(DL_ERR_INVALID, "dl_mix_round: tile_cols %d does not fit this graph "
-                                        "(%d rows); query dl_mix_plan_query on row-major args",
-                        a->tile_cols, R);
-        int64_t n_tiles = (a->n_params + a->tile_cols - 1) / a->tile_cols;
-        // tile groups: a halo round of few source rows (the split scheme's boundary launch,
-        // 276 rows at 16 columns: 18 KB a tile, latency-bound) walks g <= 8 consecutive data tiles
-        // as one kernel tile of 4cg columns, at <= 4 row passes per thread (the halo kernel's
-        // limit); DLAMD_TILE_GROUP=g caps g (1: off, a measurement knob)
-        int g = 1, cg = c;
-        int64_t lds_g = lds;
-        if (a->n_halo > 0) {
-            int gcap = 8;
-            if (const char *v = getenv("DLAMD_TILE_GROUP")) gcap = atoi(v);
-            for (int gg = 8; gg >= 2; gg >>= 1) {
-                if (gg > gcap) continue;
-                const int cc = c * gg;
-                const int64_t l = (int64_t)R * cc * 16 + csr +
-                                  (want_dev ? (int64_t)(dl::kTileThreads / 64) * cc * 16 : 0);
-                if (cc > dl::kMaxChunks || n_tiles % gg ||
-                    (int64_t)R * cc > 4 * (int64_t)dl::kTileThreads || l > dl::kLdsBytes)
-                    continue;
-                g = gg;
-                cg = cc;
-                lds_g = l;
-                break;
-            }
-        }
-        n_tiles /= g;
-        // two 1024-thread workgroups per CU when LDS allows, except at C = 4, where the second
-        // workgroup's LDS traffic (4 rows of 64 B per 16 lanes: the most bank conflicts of any
-        // C) costs more than its extra loads in flight (measured 5.5 vs 5.8 TB/s at N = 1024;
-        // the c4 rank of 8's 608-row halo round: 69.1 vs 70.1 % of spec, profiles/r11/session_c)
-        int bpc = (int)(dl::kLdsBytes / lds_g);
-        if (bpc > wg_per_cu_cap()) bpc = wg_per_cu_cap();
-        if (cg == 4) bpc = 1;
-        // two 1024-thread workgroups share a CU only at <= 64 VGPRs.  Of the column-tiled halo
-        // instantiations only those mix_tile.hip's tile_waves_per_eu caps are that small (C >= 8
-        // at <= 3 row passes without the lagged deviation: 53-64 VGPRs, no spills); every other
-        // one takes 66-123 (profiles/r13/vgprs.txt), so a grid sized for two would only queue
-        // them (rank-of 4 / 2 halo mix 1.5 / 2 % slower, profiles/r12/halo_grid/)
-        if (a->n_halo > 0) {
-            const int64_t slots = dl::kTileThreads / cg;
-            const bool capped = cg >= 8 && (R + slots - 1) / slots <= 3 && !a->mean_prev &&
-                                !a->colsum_out;
-            if (!capped) bpc = 1;
-        }
-        const int64_t grid =
-            balanced_grid(n_tiles, (int64_t)device_cus() * (bpc < 1 ? 1 : bpc) *
-                                   grid_mult_for(n_tiles, (int64_t)device_cus() *
-                                                              (bpc < 1 ? 1 : bpc)));
-        pl->pub.path = 1;
-        pl->pub.tile_cols = a->tile_cols;
-        pl->pub.grid = (int32_t)grid;
-        pl->pub.lds_bytes = (int32_t)lds_g;
-        pl->pub.n_tiles = (int32_t)n_tiles;
-        pl->pub.regular = reg;
-        pl->chunks = cg;
-        pl->grp = g;
-        pl->csr_off = (uint32_t)((int64_t)R * cg * 16);
-        pl->scratch_off = (uint32_t)((int64_t)R * cg * 16 + csr);
-        return DL_OK;
-    }
-    if ((force_reg || (prefer_reg_tail(a->W, R, 1) && !force_gather)) && R <= 65535 &&
-        a->n_params % 4 == 0 && plan_reg(a, 1, want_dev, pl))
-        return DL_OK;
-    // with the fused deviation, prefer the widest tile at <= 4 row passes per thread: the
-    // kernel then keeps each lane's deviation partials in registers and reduces them once per
-    // launch (mix_tile.hip LD); c3's 256 agents: 64-column tiles, 116 -> 105 us a round
-    // (scripts/c3_round_probe.py, profiles/r12/c3_round)
-    int cdev = 0;
-    if (want_dev)
-        for (int c = cmax; c >= 2; c >>= 1)
-            if ((int64_t)R * c <= 4 * (int64_t)dl::kTileThreads) {
-                cdev = c;
-                break;
-            }
-    // ... and one workgroup per CU there: c3 3704-3729 against 3589-3610 steps/s with two
-    // (same box, profiles/r12/c3_round/c3_rows_wg*.log)
-    bool one_per_cu = false;
-    if (cdev > 0 && cdev < cmax && a->n_params % (4 * cdev) == 0) {
-        cmax = cdev;
-        one_per_cu = true;
-    }
-    if (csr > 0 && R <= 65535 && !force_gather) {
-        for (int c = cmax; c >= 1; c >>= 1) {
-            if ((int64_t)R * c > (int64_t)dl::kRowsPerThread * dl::kTileThreads) continue;
-            const int64_t tile = (int64_t)R * c * 16;
-            const int64_t scratch = want_dev ? (int64_t)(dl::kTileThreads / 64) * c * 16 : 0;
-            const int64_t lds = tile + csr + scratch;
-            if (lds > dl::kLdsBytes) continue;
-            const int64_t T = 4 * c;
-            const int64_t n_tiles = (a->n_params + T - 1) / T;
-            if (n_tiles > 0x7fffffff) continue;
-            int bpc = (int)(dl::kLdsBytes / lds);
-            if (bpc > wg_per_cu_cap()) bpc = wg_per_cu_cap();  // 1024 threads: <= 2 per CU
-            if (one_per_cu && c == cmax) bpc = 1;
-            const int64_t grid =
-                balanced_grid(n_tiles, (int64_t)device_cus() * bpc);
-            pl->pub.path = 1;
-            pl->pub.tile_cols = (int32_t)T;
-            pl->pub.grid = (int32_t)grid;
-            pl->pub.lds_bytes = (int32_t)lds;
-            pl->pub.n_tiles = (int32_t)n_tiles;
-            pl->pub.regular = reg;
-            pl->chunks = c;
-            pl->csr_off = (uint32_t)tile;
-            pl->scratch_off = (uint32_t)(tile + csr);
-            return DL_OK;
-        }
-    }
-    if (R <= 65535 && !force_gather) {
-        if (a->n_params % 4 == 0 && plan_reg(a, 1, want_dev, pl)) return DL_OK;
-    }
-    if (a->W.n_rows > 4 * 65535)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_round: %d rows exceed the gather path limit",
-                    a->W.n_rows);
-    if (a->mean_prev || a->colsum_out)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_round: the lagged halo deviation needs the LDS "
-                                        "tile kernel; this graph takes the gather path");
-    if (local_src(a) != a->W.n_rows)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_round: n_local_src != n_rows needs the LDS tile "
-                                        "kernel; this graph takes the gather path");
-    pl->pub.path = 2;
-    pl->pub.grid = (int32_t)(((a->n_params + 255) / 256) * ((a->W.n_rows + 3) / 4));
-    pl->pub.regular = reg;
-    return DL_OK;
+    return plan_with(dl::plan_mix, a, dl::read_knobs(), pl);
 }
+int plan_rounds(const dl_mix_args *a, Plan *pl) {
+    return plan_with(dl::plan_rounds, a, dl::read_knobs(), pl);
+}
+inline int32_t local_src(const dl_mix_args *a) { return dl::local_src(*a); }
 
 int check_mix_args(const dl_mix_args *a) {
     if (!a) return fail(DL_ERR_INVALID, "dl_mix_round: args is NULL");
@@ -558,22 +234,18 @@ dl::TileArgs tile_args(const dl_mix_args *a) {
     }
     t.n_params = a->n_params;
     t.lr = a->lr;
-    bool vec = aligned16(a->x) && aligned16(a->y) && a->ldx % 4 == 0 && a->ldy % 4 == 0;
-    if (a->g) vec = vec && aligned16(a->g) && a->ldg % 4 == 0;
-    if (a->halo) vec = vec && aligned16(a->halo) && a->ldh % 4 == 0;
-    if (a->mean) vec = vec && aligned16(a->mean);
-    if (a->mean_prev) vec = vec && aligned16(a->mean_prev);
-    if (a->colsum_out) vec = vec && aligned16(a->colsum_out);
+    // float4 access: every operand given 16-byte aligned, and row-major rows too (ld % 4)
+    bool vec = aligned16(a->x) && aligned16(a->y) && aligned16(a->g) && aligned16(a->halo) &&
+               aligned16(a->mean) && aligned16(a->mean_prev) && aligned16(a->colsum_out);
+    if (a->tile_cols <= 0)
+        vec = vec && a->ldx % 4 == 0 && a->ldy % 4 == 0 && (!a->g || a->ldg % 4 == 0) &&
+              (!a->halo || a->ldh % 4 == 0);
     t.mean_prev = a->mean_prev;
     t.colsum_out = a->colsum_out;
     // the float4 kernel addresses rows with 32-bit byte offsets from the tile base
     const int64_t lim = (int64_t)1 << 32;
     const int64_t R = t.n_loc > t.n_rows ? t.n_loc : t.n_rows;
     if (a->tile_cols > 0) {
-        vec = aligned16(a->x) && aligned16(a->y) && (!a->g || aligned16(a->g)) &&
-              (!a->mean || aligned16(a->mean)) && (!a->halo || aligned16(a->halo)) &&
-              (!a->mean_prev || aligned16(a->mean_prev)) &&
-              (!a->colsum_out || aligned16(a->colsum_out));
         t.tiled = 1;
         // per-peer halo blocks (check_mix_args: <= kMaxHaloBlocks, rows summing to n_halo,
         // the whole halo < 4 GiB)
@@ -597,6 +269,23 @@ dl::TileArgs tile_args(const dl_mix_args *a) {
     t.vec = vec ? 1 : 0;
     t.mean = a->mean;
     return t;
+}
+
+// FAST-path strides (TileArgs) for tiles of T columns; a column-tiled operand's tile stride is
+// its block rows (ld*, 0 = its own rows) x T floats
+void set_tile_strides(dl::TileArgs &t, const dl_mix_args *a, int64_t T) {
+    if (t.tiled) {
+        t.xts = (a->ldx ? a->ldx : (int64_t)t.n_loc) * T * 4;
+        t.gts = (a->ldg ? a->ldg : (int64_t)t.n_loc) * T * 4;
+        t.yts = (a->ldy ? a->ldy : (int64_t)t.n_rows) * T * 4;
+        t.xrs = t.grs = t.yrs = (uint32_t)(T * 4);
+    } else {
+        t.xts = t.gts = t.yts = T * 4;
+        t.xrs = (uint32_t)(a->ldx * 4);
+        t.grs = (uint32_t)(a->ldg * 4);
+        t.yrs = (uint32_t)(a->ldy * 4);
+        t.hrs = (uint32_t)(a->ldh * 4);
+    }
 }
 
 // Deviation of x (n_rows x n_params) via the two-pass path: mean (given or column mean), then
@@ -639,180 +328,6 @@ int zero_deviation(int32_t n_rows, float *dev_sq, float *dev_max, hipStream_t s)
     return DL_OK;
 }
 
-// Configuration of the multi-round kernel: two tile images of all agents in LDS beside the CSR.
-// Returns DL_ERR_UNSUPPORTED (no message needed by callers that fall back) when it cannot run.
-int plan_rounds(const dl_mix_args *a, Plan *pl) {
-    std::memset(pl, 0, sizeof *pl);
-    const int32_t R = a->W.n_rows;
-    const bool want_dev = a->dev_sq || a->dev_max || a->mean;
-    pl->dev = want_dev;
-    if (a->n_halo > 0 || local_src(a) != a->W.n_rows)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds: halo rows need one exchange per round");
-    if (want_dev && !a->W.doubly_stochastic)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds: the fused final deviation needs a doubly "
-                                        "stochastic W");
-    const int reg = a->W.uniform_row_nnz > 0 ? 1 : 0;
-    const int32_t n_w = (reg && a->W.shared_row_weights) ? a->W.uniform_row_nnz : a->W.nnz;
-    if (dl::csr_lds_bytes(R, a->W.nnz, reg, n_w) == 0 || R > 65535)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds: CSR too large");
-    auto fits = [&](int c) {
-        // degree-4 regular graphs with shared weights keep the CSR in registers (mix_multi.hip
-        // launch_kv: uniform_row_nnz 5, 5 weights, <= 4 rows per thread): no LDS for it
-        const bool in_regs = a->W.uniform_row_nnz == 5 && n_w == 5 &&
-                             dl::tile_passes(c, R, true) <= 4;
-        const uint32_t csr = in_regs ? 0u : dl::csr_lds_bytes(R, a->W.nnz, reg, n_w);
-        const int64_t tile = (int64_t)R * c * 16;
-        const int64_t scratch = want_dev ? (int64_t)(dl::kTileThreads / 64) * c * 16 : 0;
-        return (int64_t)R * c <= (int64_t)dl::kRowsPerThread * dl::kTileThreads &&
-               2 * tile + csr + scratch <= dl::kLdsBytes;
-    };
-    int c = 0;
-    if (a->tile_cols > 0) {
-        c = a->tile_cols / 4;
-        if (!fits(c))
-            return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds: two %d-column tiles of %d rows do "
-                                            "not fit LDS", a->tile_cols, R);
-    } else {
-        for (int cc = next_pow2_chunks(a->n_params); cc >= 1; cc >>= 1)
-            if (fits(cc) && a->n_params % (4 * cc) == 0) {
-                c = cc;
-                break;
-            }
-        if (c == 0)
-            return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds: no full-tile row-major configuration");
-    }
-    const int64_t T = 4 * c;
-    const int64_t n_tiles = (a->n_params + T - 1) / T;
-    const int64_t tile = (int64_t)R * c * 16;
-    const bool in_regs = a->W.uniform_row_nnz == 5 && n_w == 5 && dl::tile_passes(c, R, true) <= 4;
-    const uint32_t csr = in_regs ? 0u : dl::csr_lds_bytes(R, a->W.nnz, reg, n_w);
-    pl->chunks = c;
-    pl->csr_off = (uint32_t)(2 * tile);
-    pl->scratch_off = (uint32_t)(2 * tile + csr);
-    pl->pub.path = 3;
-    pl->pub.tile_cols = (int32_t)T;
-    pl->pub.grid = (int32_t)balanced_grid(n_tiles, device_cus());
-    pl->pub.lds_bytes = (int32_t)(2 * tile + csr +
-                                  (want_dev ? (dl::kTileThreads / 64) * c * 16 : 0));
-    pl->pub.n_tiles = (int32_t)n_tiles;
-    pl->pub.regular = reg;
-    return DL_OK;
-}
-
-// dl_mix_rounds_trace configuration: one agent per thread, C float4 column chunks per step.
-struct TracePlan {
-    int32_t max_rounds;  // rounds per traced pass (the per-round deviations live in VGPRs)
-    int32_t grid, chunks;
-    int64_t n_steps;
-    uint32_t csr_off, scratch_off, lds;
-    int32_t irr;   // 1: mix_trace_irr_kernel (one image, register head + LDS tail)
-    int32_t head;  // irr: CSR entries per row in registers
-    int32_t gm;    // irr: W not doubly stochastic, every round's mean from its outputs
-    int32_t narrow;  // irr: 2-column steps, 6-byte tail entries
-};
-
-// mix_trace_irr_kernel's configuration: one [N] float4 image, each row's first `head` entries in
-// registers and the rest as 8-byte {weight, row} pairs behind it, a 16 x float4 mean scratch.
-// The tail's u16 row map (setup only) lives in the image area.
-int plan_trace_irr(const dl_mix_args *a, TracePlan *tp) {
-    const dl_csr &W = a->W;
-    const int32_t N = W.n_rows;
-    if (N < 2 || N > 4 * dl::kTileThreads || W.nnz > 65535 + 5 * (int64_t)N)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: no traced kernel for %d agents "
-                                        "with %d CSR entries", N, W.nnz);
-    int head = dl::reg_head_rows(W.min_row_nnz);
-    int64_t ntail = (int64_t)W.nnz - (int64_t)head * N;
-    if (ntail > 65535 || ntail < 0) {
-        head = 0;
-        ntail = W.nnz;
-    }
-    if (ntail > 65535)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: %lld CSR entries past the register "
-                                        "heads (> 65535)", (long long)ntail);
-    // 4-column steps with 8-byte {weight, row} tail pairs (the tail's row map in the image), or
-    // 2-column steps with 6-byte tail entries when that does not fit
-    bool narrow = false;
-    uint32_t img = (uint32_t)N * 16u;
-    uint32_t tail = (uint32_t)align_up((size_t)ntail * 8);
-    if (2 * ntail > (int64_t)img || img + tail + 256u > (uint32_t)dl::kLdsBytes) {
-        narrow = true;
-        img = (uint32_t)align_up((size_t)N * 8u);
-        tail = (uint32_t)align_up((size_t)ntail * 6);
-        if (img + tail + 256u > (uint32_t)dl::kLdsBytes)
-            return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: the CSR of %d agents (%d "
-                                            "entries) does not fit LDS beside one image", N, W.nnz);
-    }
-    tp->irr = 1;
-    tp->head = head;
-    tp->gm = W.doubly_stochastic ? 0 : 1;
-    tp->narrow = narrow ? 1 : 0;
-    tp->chunks = 1;
-    tp->csr_off = img;
-    tp->scratch_off = img + tail;
-    tp->lds = img + tail + 256u;
-    tp->max_rounds = dl::irr_trace_rounds(dl::irr_trace_kv(N));
-    tp->n_steps = a->n_params / (narrow ? 2 : 4);
-    tp->grid = (int32_t)balanced_grid(tp->n_steps, device_cus());
-    return DL_OK;
-}
-
-int plan_trace(const dl_mix_args *a, TracePlan *tp) {
-    const int32_t N = a->W.n_rows;
-    std::memset(tp, 0, sizeof *tp);
-    if (a->n_halo > 0 || local_src(a) != a->W.n_rows)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: halo rows need one exchange per "
-                                        "round");
-    if (a->g)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: no local step (g must be NULL)");
-    if (a->n_params % 4)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: n_params must be a multiple of 4");
-    // a W that is not doubly stochastic (every round's mean from its outputs), or an irregular
-    // graph above 2048 agents: the one-image kernel with the register head + LDS tail CSR
-    if (!a->W.doubly_stochastic)
-        return plan_trace_irr(a, tp);
-    if (N > 2 * dl::kTileThreads && !(a->W.uniform_row_nnz == 5 && a->W.shared_row_weights))
-        return plan_trace_irr(a, tp);
-    // one agent per thread up to 1024 agents; above, mix_trace_wide_kernel (one column chunk per
-    // step, up to 4 agents per thread; the CSR in registers above 2048 agents)
-    if (N < 2 || N > 4 * dl::kTileThreads)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: needs 2..%d agents, got %d",
-                    4 * dl::kTileThreads, N);
-    if (a->n_params % 4)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: n_params must be a multiple of 4");
-    const int reg = a->W.uniform_row_nnz > 0 ? 1 : 0;
-    const int32_t n_w = (reg && a->W.shared_row_weights) ? a->W.uniform_row_nnz : a->W.nnz;
-    const bool in_regs = a->W.uniform_row_nnz == 5 && n_w == 5;
-    const uint32_t csr = in_regs ? 0u : dl::csr_lds_bytes(N, a->W.nnz, reg, n_w);
-    if (!in_regs && csr == 0) return plan_trace_irr(a, tp);
-    const bool wide = N > dl::kTileThreads;
-    if (wide && !in_regs && N > 2 * dl::kTileThreads)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: above %d agents the traced pass "
-                                        "keeps the CSR in registers (regular degree-4 graphs with "
-                                        "shared weights)", 2 * dl::kTileThreads);
-    const int64_t nq = a->n_params / 4;
-    const int64_t lc = a->tile_cols > 0 ? a->tile_cols / 4 : 0;   // 0: row-major
-    // widest chunk count whose two images fit LDS (a round then does C outputs per thread)
-    tp->chunks = 0;
-    for (int c = wide ? 1 : 4; c >= 1; c >>= 1) {
-        const uint32_t img = 2u * (uint32_t)N * 16u * (uint32_t)c;
-        const uint32_t scr = (uint32_t)align_up(img + csr);
-        const uint32_t lds = scr + (dl::kTileThreads / 64) * 16u * (uint32_t)c;
-        // a step's chunks must be whole (nq % c) and lie in one operand tile (lc % c)
-        if (lds <= (uint32_t)dl::kLdsBytes && nq % c == 0 && (lc == 0 || lc % c == 0)) {
-            tp->chunks = c;
-            tp->csr_off = img;
-            tp->scratch_off = scr;
-            tp->lds = lds;
-            break;
-        }
-    }
-    if (tp->chunks == 0) return plan_trace_irr(a, tp);   // two images do not fit: one image
-    tp->max_rounds = dl::trace_max_rounds(N, in_regs, tp->chunks);
-    tp->n_steps = nq / tp->chunks;
-    tp->grid = (int32_t)balanced_grid(tp->n_steps, device_cus());
-    return DL_OK;
-}
-
 }  // namespace
 
 namespace dl {
@@ -829,7 +344,7 @@ int dl_mix_trace_plan(const dl_mix_args *args, int32_t *max_rounds) {
     int rc = check_mix_args(args);
     if (rc) return rc;
     TracePlan tp;
-    rc = plan_trace(args, &tp);
+    rc = plan_with(dl::plan_trace, args, dl::read_knobs(), &tp);
     if (rc) return rc;
     *max_rounds = tp.max_rounds;
     return DL_OK;
@@ -846,8 +361,9 @@ int dl_mix_rounds_trace(const dl_mix_args *args, int32_t rounds, float *trace, v
     int rc = check_mix_args(args);
     if (rc) return rc;
     if (!trace) return fail(DL_ERR_INVALID, "dl_mix_rounds_trace: trace is NULL");
+    const dl::Knobs knobs = dl::read_knobs();
     TracePlan tp;
-    rc = plan_trace(args, &tp);
+    rc = plan_with(dl::plan_trace, args, knobs, &tp);
     if (rc) return rc;
     if (rounds < 1 || rounds > tp.max_rounds)
         return fail(DL_ERR_INVALID, "dl_mix_rounds_trace: rounds must be in [1, %d] (one "
@@ -859,18 +375,9 @@ int dl_mix_rounds_trace(const dl_mix_args *args, int32_t rounds, float *trace, v
     const int32_t N = args->W.n_rows;
     if (tp.irr && t.tiled && args->tile_cols % 4)
         return fail(DL_ERR_INVALID, "dl_mix_rounds_trace: tile_cols must be a multiple of 4");
-    if (t.tiled) {
-        const int64_t T = args->tile_cols;
-        t.lchunks = (int32_t)(T / 4);
-        t.xts = (args->ldx ? args->ldx : (int64_t)N) * T * 4;
-        t.yts = (args->ldy ? args->ldy : (int64_t)N) * T * 4;
-        t.xrs = t.yrs = (uint32_t)(T * 4);
-    } else {
-        t.lchunks = 1;
-        t.xts = t.yts = 16;
-        t.xrs = (uint32_t)(args->ldx * 4);
-        t.yrs = (uint32_t)(args->ldy * 4);
-    }
+    // a step walks float4 chunks: of an operand tile when column-tiled, else of the row itself
+    t.lchunks = t.tiled ? args->tile_cols / 4 : 1;
+    set_tile_strides(t, args, t.tiled ? args->tile_cols : 4);
     t.n_tiles = (int32_t)tp.n_steps;
     t.csr_off = tp.csr_off;
     t.scratch_off = tp.scratch_off;
@@ -884,7 +391,8 @@ int dl_mix_rounds_trace(const dl_mix_args *args, int32_t rounds, float *trace, v
                                                       rounds, tp.grid,
                                                       (int)tp.lds, trace,
                                                       static_cast<hipStream_t>(stream))
-                          : dl::launch_mix_trace(t, tp.chunks, rounds, tp.grid, (int)tp.lds, trace,
+                          : dl::launch_mix_trace(t, tp.chunks, knobs.trace_planes, rounds, tp.grid,
+                                                 (int)tp.lds, trace,
                                                  static_cast<hipStream_t>(stream));
     return e == hipSuccess ? DL_OK : hip_fail(e, "mix_trace_kernel launch");
 }
@@ -916,18 +424,7 @@ int dl_mix_rounds(const dl_mix_args *args, int32_t rounds, void *workspace, size
     if (!t.vec)
         return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds: operands must be 16-byte aligned float4 "
                                         "rows");
-    const int64_t T = pl.pub.tile_cols;
-    if (t.tiled) {
-        t.xts = (args->ldx ? args->ldx : (int64_t)Nr) * T * 4;
-        t.gts = (args->ldg ? args->ldg : (int64_t)Nr) * T * 4;
-        t.yts = (args->ldy ? args->ldy : (int64_t)Nr) * T * 4;
-        t.xrs = t.grs = t.yrs = (uint32_t)(T * 4);
-    } else {
-        t.xts = t.gts = t.yts = T * 4;
-        t.xrs = (uint32_t)(args->ldx * 4);
-        t.grs = (uint32_t)(args->ldg * 4);
-        t.yrs = (uint32_t)(args->ldy * 4);
-    }
+    set_tile_strides(t, args, pl.pub.tile_cols);
     t.n_tiles = pl.pub.n_tiles;
     t.col_base = 0;
     t.csr_off = pl.csr_off;
@@ -1051,8 +548,8 @@ const char *dl_last_error(void) { return g_err.c_str(); }
 size_t dl_mix_workspace_bytes(int32_t n_rows, int32_t n_halo, int64_t n_params) {
     (void)n_halo;
     if (n_rows < 0 || n_params < 0) return 0;
-    return align_up((size_t)max_parts() * (size_t)n_rows * 4) + align_up((size_t)n_params * 4) +
-           kAlign;
+    const size_t parts = (size_t)dl::max_parts(device_cus(), dl::read_knobs());
+    return align_up(parts * (size_t)n_rows * 4) + align_up((size_t)n_params * 4) + kAlign;
 }
 
 int dl_mix_plan_query(const dl_mix_args *args, dl_mix_plan *plan) {
@@ -1104,23 +601,12 @@ int plan_from_csr(const dl_csr &W, int32_t n_halo, int64_t n_params, int32_t dev
     a.n_params = n_params;
     float dummy;
     if (deviation) a.dev_max = &dummy;
-    if (tile_cols == -1) {  // pick the column-tiled width (a tile of every source row in LDS)
-        const int reg = W.uniform_row_nnz > 0 ? 1 : 0;
-        const int32_t n_w = (reg && a.W.shared_row_weights) ? W.uniform_row_nnz : W.nnz;
-        const int64_t R = (int64_t)W.n_rows + n_halo;
-        const int c = R > 65535 ? 0
-                                : choose_tiled_chunks(a.W, (int32_t)R,
-                                                      dl::csr_lds_bytes(W.n_rows, W.nnz, reg, n_w),
-                                                      deviation != 0, n_halo > 0);
-        tile_cols = 4 * c;   // 0: not tileable, report the row-major plan
-        // a tiled halo round needs whole tiles (check_mix_args)
-        if (n_halo > 0 && tile_cols > 0)
-            while (tile_cols > 4 && n_params % tile_cols) tile_cols >>= 1;
-        if (n_halo > 0 && tile_cols > 0 && n_params % tile_cols) tile_cols = 0;
-    }
-    a.tile_cols = tile_cols;
+    const dl::Knobs k = dl::read_knobs();
+    // -1: pick the column-tiled width (a tile of every source row in LDS)
+    a.tile_cols = tile_cols == -1 ? dl::choose_tile_cols(a.W, n_halo, n_params, deviation != 0, k)
+                                  : tile_cols;
     Plan pl;
-    int rc = plan_mix(&a, &pl);
+    int rc = plan_with(dl::plan_mix, &a, k, &pl);
     if (rc) return rc;
     *plan = pl.pub;
     return DL_OK;
@@ -1179,21 +665,9 @@ int dl_mix_round(const dl_mix_args *args, void *workspace, size_t ws_bytes, dl_s
         // operands) on the guarded one; each launch writes its own deviation partial rows
         const bool reg_csr = pl.pub.path == 4 || pl.pub.path == 5;
         const int64_t T = pl.pub.tile_cols;
-        if (t.tiled) {
-            if (!t.vec)
-                return fail(DL_ERR_INVALID, "dl_mix_round: tiled operands must be 16-byte aligned");
-            // tile stride = the operand's block rows (ld*, 0 = its own rows) x T floats
-            t.xts = (args->ldx ? args->ldx : t.n_loc) * T * 4;
-            t.gts = (args->ldg ? args->ldg : t.n_loc) * T * 4;
-            t.yts = (args->ldy ? args->ldy : (int64_t)Nr) * T * 4;
-            t.xrs = t.grs = t.yrs = (uint32_t)(T * 4);
-        } else {
-            t.xts = t.gts = t.yts = T * 4;
-            t.xrs = (uint32_t)(args->ldx * 4);
-            t.grs = (uint32_t)(args->ldg * 4);
-            t.yrs = (uint32_t)(args->ldy * 4);
-            t.hrs = (uint32_t)(args->ldh * 4);
-        }
+        if (t.tiled && !t.vec)
+            return fail(DL_ERR_INVALID, "dl_mix_round: tiled operands must be 16-byte aligned");
+        set_tile_strides(t, args, T);
         const int64_t n_full = t.tiled ? pl.pub.n_tiles : (t.vec ? args->n_params / T : 0);
         const int64_t n_tail = pl.pub.n_tiles - n_full;  // 0 or 1 when vec, else all tiles
         int grid_full = (int)(n_full < pl.pub.grid ? n_full : pl.pub.grid);
@@ -1298,7 +772,7 @@ namespace {
 int deviation_one_pass(const float *x, int64_t ldx, int32_t tile_cols, int32_t n_rows,
                        int64_t n_params, float *dev_sq, float *dev_max, float *mean_out, char *ws,
                        size_t ws_bytes, hipStream_t s) {
-    int c = tile_cols > 0 ? tile_cols / 4 : next_pow2_chunks(n_params);
+    int c = tile_cols > 0 ? tile_cols / 4 : dl::next_pow2_chunks(n_params);
     for (; c >= 1; c >>= 1) {
         if ((int64_t)n_rows * c <= (int64_t)dl::kRowsPerThread * dl::kTileThreads) break;
         if (tile_cols > 0) return DL_ERR_UNSUPPORTED;

@@ -5,12 +5,9 @@
 
 #include <cstdlib>
 
-namespace dl {
+#include "plan.h"   // tile geometry shared with the planner: k* constants, tile_kv, trace rounds
 
-constexpr int kTileThreads = 1024;      // 16 waves: one workgroup per CU owns a column tile
-constexpr int kRowsPerThread = 8;       // prefetch depth: rows x chunks <= 8 * 1024 float4
-constexpr int kLdsBytes = 163840;       // 160 KiB LDS per CU on gfx950
-constexpr int kMaxChunks = 32;          // T <= 128 columns per tile
+namespace dl {
 
 struct TileArgs {
     const float *x;
@@ -76,14 +73,10 @@ struct TileArgs {
 };
 constexpr int kMaxHaloBlocks = 16;
 
-// LDS bytes the staged CSR needs (0 if it cannot be staged: > 65535 rows/entries).
 // Raise kernel k's dynamic-LDS limit to the whole CU (kLdsBytes), once per (kernel, device):
 // launches then make no attribute call, so they are capturable in a hipGraph and carry no
 // per-launch driver work.
 hipError_t allow_full_lds(const void *k);
-
-// n_w = weights staged (nnz, or the row degree when all rows share one weight sequence).
-uint32_t csr_lds_bytes(int32_t n_rows, int32_t nnz, int32_t regular, int32_t n_w);
 
 hipError_t launch_mix_tile(const TileArgs &a, int chunks, bool sgd, bool dev, bool mix, int grid,
                            int lds_bytes, bool fast, hipStream_t s);
@@ -96,57 +89,23 @@ inline bool tile_lag(const TileArgs &a) {
     return tile_partitioned(a) && (a.mean_prev != nullptr || a.colsum_out != nullptr);
 }
 hipError_t launch_mix_gather(const TileArgs &a, bool sgd, hipStream_t s);
-// Tile kernel with the CSR in registers (regular graphs of 5 entries per row whose CSR does not
-// fit LDS beside the tile): FAST path only, no halo, chunks 1, <= 4 rows per thread.
-bool reg_csr_supported(int chunks, int n_rows, int regular, int n_halo);
-// ... and its irregular form: every row has >= min_row_nnz entries; the first reg_head_rows()
-// of each row in registers, the remaining nnz - head * n_rows entries in LDS (8 B each)
-int reg_head_rows(int min_row_nnz);   // 5, 3, 2 or 0 (no register head)
-bool reg_tail_supported(int chunks, int n_rows, int head, int n_halo);
-// head 0: the regular register-CSR kernel (path 4); head > 0: head + LDS tail (path 5), the
-// tail as {weight, row} pairs of 8 B (tail_fmt 2, heads < 5) or weights + u16 rows (1: 6 B)
+// The register-CSR tile kernels (plan.h reg_csr_supported / reg_tail_supported).  head 0: the
+// regular one (path 4); head > 0: head + LDS tail (path 5), the tail as {weight, row} pairs of
+// 8 B (tail_fmt 2, heads < 5) or weights + u16 rows (1: 6 B)
 hipError_t launch_mix_tile_reg(const TileArgs &a, int chunks, int head, int tail_fmt, bool sgd,
                                bool dev, int grid, int lds, hipStream_t s);
-// rows per thread (KV) the FAST tile kernels use for n_src rows at `chunks` float4 per row
-int tile_passes(int chunks, int n_src, bool fast);
 // K rounds of mixing on LDS-resident tiles (mix_multi.hip); FAST tiles only, no halo rows
 hipError_t launch_mix_multi(const TileArgs &a, int chunks, int rounds, bool sgd, bool dev,
                             int grid, int lds, hipStream_t s);
 // K rounds on LDS-resident column chunks with the per-round max deviation trace
-// (mix_trace.hip): mix_trace_kernel + trace_reduce into trace_out[rounds]
-constexpr int kTraceRounds = 32;   // rounds per traced pass (per-round deviations in VGPRs)
-// mix_trace_rows_kernel at 4 agents per thread keeps 4 agents' CSR offsets and prefetch
-// registers: its trace depth is capped so the per-round deviations fit VGPRs (122, no spills)
-constexpr int kRowsTraceRounds = 24;
-// mix_trace_wide_kernel (1024 < N <= 4096 agents, one chunk per step, KV = 2 or 4 agents per
-// thread) keeps every agent's per-round deviation of the pass in registers (KV x rounds VGPRs):
-// 16 rounds per pass at KV = 2, 8 at KV = 4 (12 spilled 20-30 VGPRs there)
-constexpr int kWideTraceRounds2 = 16;
-constexpr int kWideTraceRounds4 = 8;
-inline int wide_trace_rounds(int n_rows) {
-    return n_rows > 2 * kTileThreads ? kWideTraceRounds4 : kWideTraceRounds2;
-}
-// the agent-major traced kernel serves register-cached regular graphs at C = 4;
-// DLAMD_TRACE_PLANES=1 keeps the chunk-major planes kernel (comparison runs)
-inline bool trace_uses_rows(int n_rows, bool in_regs, int chunks) {
-    return in_regs && chunks == 4 && n_rows <= kTileThreads &&
-           std::getenv("DLAMD_TRACE_PLANES") == nullptr;
-}
-inline int trace_max_rounds(int n_rows, bool in_regs, int chunks) {
-    if (n_rows > kTileThreads) return wide_trace_rounds(n_rows);
-    return trace_uses_rows(n_rows, in_regs, chunks) && n_rows > kTileThreads / 2 ? kRowsTraceRounds
-                                                                                  : kTraceRounds;
-}
-hipError_t launch_mix_trace(const TileArgs &a, int chunks, int rounds, int grid, int lds,
-                            float *trace_out, hipStream_t s);
+// (mix_trace.hip): mix_trace_kernel + trace_reduce into trace_out[rounds]; at most
+// trace_max_rounds() rounds (plan.h).  planes: Knobs::trace_planes
+hipError_t launch_mix_trace(const TileArgs &a, int chunks, bool planes, int rounds, int grid,
+                            int lds, float *trace_out, hipStream_t s);
 // mix_trace_irr_kernel (one image, register head + LDS tail of 8-byte pairs, one 4-column
 // chunk per step): irregular graphs of more than 2048 agents and W that are not doubly
 // stochastic (general_mean: every round's column mean from its outputs).  KV agents per thread,
-// irr_trace_rounds(KV) rounds per pass.
-constexpr int irr_trace_kv(int n_rows) {
-    return n_rows <= kTileThreads ? 1 : n_rows <= 2 * kTileThreads ? 2 : 4;
-}
-constexpr int irr_trace_rounds(int kv) { return kv == 1 ? 24 : kv == 2 ? 12 : 4; }
+// irr_trace_rounds(KV) rounds per pass (plan.h).
 // narrow: 2-column steps (8-byte image entries) and a 6-byte LDS tail, for larger CSRs
 hipError_t launch_mix_trace_irr(const TileArgs &a, int head, bool general_mean, bool narrow,
                                 int rounds, int grid, int lds, float *trace_out, hipStream_t s);

@@ -177,11 +177,12 @@ __device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
 //        for tails that do not fit LDS at 8 B).  The fold runs the
 //        register head, then the tail, in CSR order: still the reference's left fold.
 // Waves per SIMD the compiler must leave room for: 8 (<= 64 VGPRs, two 1024-thread workgroups
-// per CU) for the grouped halo launch of few rows (C >= 8 at <= 3 passes, the split scheme's
-// boundary launch, latency-bound at one workgroup a CU), else no constraint
+// per CU) for the grouped halo launch of few rows (plan.h halo_two_per_cu, which also sizes the
+// grid: the split scheme's boundary launch, latency-bound at one workgroup a CU), else no
+// constraint
 template <int C, int KV, int HALO, bool LAG>
 constexpr int tile_waves_per_eu() {
-    return (HALO == 2 && C >= 8 && KV <= 3 && !LAG) ? 8 : 1;
+    return (HALO == 2 && halo_two_per_cu(C, KV, LAG)) ? 8 : 1;
 }
 
 template <int C, int KV, bool SGD, bool DEV, bool MIX, int HALO, bool FAST, int RD = 0,
@@ -1040,28 +1041,22 @@ hipError_t launch_mode(const TileArgs &a, bool sgd, bool dev, bool mix, int grid
                : launch_one<C, KV, false, false, true, 0, FAST>(a, grid, lds, s);
 }
 
-// FAST kernels: every C x KV in {2,4,8}; guarded kernels: every C, KV = 8.
+// FAST kernels: every C x KV in {2,4,8}, and tile_kv's KV = 3 (a column-tiled halo mix, C <= 8);
+// guarded kernels: every C, KV = 8.
 template <int C>
 hipError_t launch_fast_c(const TileArgs &a, int kv, bool sgd, bool dev, bool mix, int grid,
                          int lds, hipStream_t s) {
-    if (kv <= 2) return launch_mode<C, 2, true>(a, sgd, dev, mix, grid, lds, s);
-    // a column-tiled halo round of 2..3 row passes (c4 at 8 GPUs: 512 + 96 rows at C = 4; at 2
-    // GPUs 2048 + 128 rows at C = 1) runs three passes instead of four: the fourth would only
-    // re-read row 0 (45 % of the staging loads dead at 608 rows, 47 % at 2176)
-    if (kv == 3 && a.tiled && a.n_src > a.n_loc && C <= 8)
-        return launch_part<C, 3, true, 2>(a, sgd, grid, lds, s);
-    if (kv <= 4) return launch_mode<C, 4, true>(a, sgd, dev, mix, grid, lds, s);
-    return launch_mode<C, 8, true>(a, sgd, dev, mix, grid, lds, s);
+    switch (kv) {
+        case 2: return launch_mode<C, 2, true>(a, sgd, dev, mix, grid, lds, s);
+        case 3:
+            if constexpr (C <= 8) return launch_part<C, 3, true, 2>(a, sgd, grid, lds, s);
+            return hipErrorInvalidValue;
+        case 4: return launch_mode<C, 4, true>(a, sgd, dev, mix, grid, lds, s);
+        default: return launch_mode<C, 8, true>(a, sgd, dev, mix, grid, lds, s);
+    }
 }
 
 }  // namespace
-
-int tile_passes(int chunks, int n_src, bool fast) {
-    const int slots = kTileThreads / chunks;
-    const int need = (n_src + slots - 1) / slots;
-    if (!fast) return kRowsPerThread;
-    return need <= 2 ? 2 : need <= 4 ? 4 : 8;
-}
 
 // Register-CSR tile kernels, FAST path, no halo rows, C = 1 (T = 4 columns), KV in {2, 4} rows
 // per thread, i.e. up to 4096 agents.  (C = 2 at KV = 4 spills; at KV = 2 -- 1024 agents -- a
@@ -1081,18 +1076,6 @@ template <int RD, int RAG>
 hipError_t launch_reg(const TileArgs &a, bool sgd, bool dev, int grid, int lds, hipStream_t s) {
     return tile_passes(1, a.n_src, true) <= 2 ? launch_reg_kv<2, RD, RAG>(a, sgd, dev, grid, lds, s)
                                               : launch_reg_kv<4, RD, RAG>(a, sgd, dev, grid, lds, s);
-}
-
-bool reg_csr_supported(int chunks, int n_rows, int regular, int n_halo) {
-    return regular == 5 && n_halo == 0 && chunks == 1 && tile_passes(chunks, n_rows, true) <= 4;
-}
-
-int reg_head_rows(int min_row_nnz) {
-    return min_row_nnz >= 5 ? 5 : min_row_nnz >= 3 ? 3 : min_row_nnz >= 2 ? 2 : 0;
-}
-
-bool reg_tail_supported(int chunks, int n_rows, int head, int n_halo) {
-    return head > 0 && n_halo == 0 && chunks == 1 && tile_passes(chunks, n_rows, true) <= 4;
 }
 
 hipError_t launch_mix_tile_reg(const TileArgs &a, int chunks, int head, int tail_fmt, bool sgd,
@@ -1120,9 +1103,7 @@ hipError_t launch_mix_tile_reg(const TileArgs &a, int chunks, int head, int tail
 hipError_t launch_mix_tile(const TileArgs &a, int chunks, bool sgd, bool dev, bool mix, int grid,
                            int lds, bool fast, hipStream_t s) {
     if (fast) {
-        int kv = tile_passes(chunks, a.n_src, true);
-        const int need = (a.n_src + kTileThreads / chunks - 1) / (kTileThreads / chunks);
-        if (need == 3 && mix && a.tiled && a.n_src > a.n_loc) kv = 3;   // (launch_fast_c)
+        const int kv = tile_kv(chunks, a.n_src, true, mix && a.tiled && a.n_src > a.n_loc);
         switch (chunks) {
             case 1: return launch_fast_c<1>(a, kv, sgd, dev, mix, grid, lds, s);
             case 2: return launch_fast_c<2>(a, kv, sgd, dev, mix, grid, lds, s);
@@ -1155,13 +1136,6 @@ hipError_t allow_full_lds(const void *k) {
     e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     if (e == hipSuccess) done.insert({k, dev});
     return e;
-}
-
-uint32_t csr_lds_bytes(int32_t n_rows, int32_t nnz, int32_t regular, int32_t n_w) {
-    if (nnz > 65535 || n_rows > 65535) return 0;
-    uint32_t b = 4u * (uint32_t)n_w + 2u * (uint32_t)nnz;
-    if (!regular) b += 2u * (uint32_t)(n_rows + 1);
-    return (b + 15u) & ~15u;
 }
 
 hipError_t launch_mix_gather(const TileArgs &a, bool sgd, hipStream_t s) {

@@ -1016,10 +1016,10 @@ hipError_t launch_mix_trace_irr(const TileArgs &a, int head, bool general_mean, 
     return hipGetLastError();
 }
 
-hipError_t launch_mix_trace(const TileArgs &a, int chunks, int rounds, int grid, int lds,
-                            float *trace_out, hipStream_t s) {
+hipError_t launch_mix_trace(const TileArgs &a, int chunks, bool planes, int rounds, int grid,
+                            int lds, float *trace_out, hipStream_t s) {
     const bool in_regs = a.regular == 5 && a.n_w == 5;
-    if (rounds < 1 || rounds > trace_max_rounds(a.n_rows, in_regs, chunks))
+    if (rounds < 1 || rounds > trace_max_rounds(a.n_rows, in_regs, chunks, planes))
         return hipErrorInvalidValue;
     hipError_t e;
     if (a.n_rows > kTileThreads) {   // the wide kernel: C = 1, KV agents per thread
@@ -1030,7 +1030,7 @@ hipError_t launch_mix_trace(const TileArgs &a, int chunks, int rounds, int grid,
                         : launch_wide<2, 0>(a, rounds, grid, lds, s);
         else
             e = launch_wide<4, 5>(a, rounds, grid, lds, s);
-    } else if (trace_uses_rows(a.n_rows, in_regs, chunks)) {
+    } else if (trace_uses_rows(a.n_rows, in_regs, chunks, planes)) {
         // agent-major rows (mix_trace_rows_kernel); DLAMD_TRACE_PLANES=1 keeps the chunk-major
         // planes for comparison
         if (a.n_rows <= 256)
