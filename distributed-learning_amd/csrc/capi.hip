@@ -1,7 +1,10 @@
-// C ABI of libdlamd.so (include/dlamd.h): argument validation, workspace carving, launches and
-// error reporting; the kernel configuration of a round comes from the planner (plan.h).  No
-// exceptions cross this boundary; every entry point returns a dl_status and leaves a thread-local
-// message for dl_last_error().
+// C ABI of libdlamd.so (include/dlamd.h): the thread-local error, the device's compute units and
+// the environment knobs, read once per call.  What a round entry point checks and launches is
+// decided by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here
+// their description of a call is turned into launch_* calls and the step after them.  The entry
+// points that are no rounds (dl_mix_until, dl_consensus_gd, the conversions, ...) check their
+// own arguments.  No exceptions cross this boundary; every entry point returns a dl_status and
+// leaves a thread-local message for dl_last_error().
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -47,29 +50,22 @@ int device_cus() {
     return cache[dev];
 }
 
-constexpr size_t kAlign = 256;
-size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// MI355X Infinity Cache (MALL), shared by all XCDs
-constexpr size_t kMallBytes = (size_t)256 << 20;
-
-bool overlaps(const void *a, size_t an, const void *b, size_t bn) {
-    const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
-    return x < y + bn && y < x + an;
-}
+using dl::align_up;
+using dl::aligned16;
+using dl::overlaps;
+constexpr size_t kAlign = dl::kWsAlign;
 
 using dl::Plan;
-using dl::TracePlan;
 
-// The planners of plan.h for the current device and environment; a failure's text goes to
-// dl_last_error().
+// A host-only function's status; a failure's text (err) goes to dl_last_error().
+int status(int rc, const char *err) { return rc ? fail(rc, "%s", err) : DL_OK; }
+
+// The planners of plan.h for the current device; a failure's text goes to dl_last_error().
 template <class P>
 int plan_with(int (*planner)(const dl_mix_args &, int, const dl::Knobs &, P *, char *),
               const dl_mix_args *a, const dl::Knobs &k, P *pl) {
     char err[dl::kErrLen];
-    const int rc = planner(*a, device_cus(), k, pl, err);
-    return rc ? fail(rc, "%s", err) : DL_OK;
+    return status(planner(*a, device_cus(), k, pl, err), err);
 }
 int plan_mix(const dl_mix_args *a, Plan *pl) {
     return plan_with(dl::plan_mix, a, dl::read_knobs(), pl);
@@ -77,215 +73,9 @@ int plan_mix(const dl_mix_args *a, Plan *pl) {
 int plan_rounds(const dl_mix_args *a, Plan *pl) {
     return plan_with(dl::plan_rounds, a, dl::read_knobs(), pl);
 }
-inline int32_t local_src(const dl_mix_args *a) { return dl::local_src(*a); }
-
 int check_mix_args(const dl_mix_args *a) {
-    if (!a) return fail(DL_ERR_INVALID, "dl_mix_round: args is NULL");
-    const dl_csr &W = a->W;
-    if (W.n_rows <= 0) return fail(DL_ERR_INVALID, "dl_mix_round: n_rows must be > 0 (got %d)", W.n_rows);
-    if (a->n_params <= 0) return fail(DL_ERR_INVALID, "dl_mix_round: n_params must be > 0");
-    if (a->n_halo < 0) return fail(DL_ERR_INVALID, "dl_mix_round: n_halo < 0");
-    if (a->n_local_src < 0) return fail(DL_ERR_INVALID, "dl_mix_round: n_local_src < 0");
-    const int32_t NL = local_src(a);
-    // an interior / boundary row set of an agent partition (outputs need not be source rows)
-    const bool part = NL != W.n_rows;
-    if ((int64_t)W.n_rows > (int64_t)NL + a->n_halo)
-        return fail(DL_ERR_INVALID, "dl_mix_round: n_rows %d > n_local_src + n_halo %lld",
-                    W.n_rows, (long long)NL + a->n_halo);
-    if (W.nnz < 0) return fail(DL_ERR_INVALID, "dl_mix_round: nnz < 0");
-    if (a->n_hub_rows < 0) return fail(DL_ERR_INVALID, "dl_mix_round: n_hub_rows < 0");
-    if (!a->x || !a->y || !W.row_ptr || (W.nnz > 0 && (!W.col || !W.w)))
-        return fail(DL_ERR_INVALID, "dl_mix_round: null x/y/row_ptr/col/w");
-    if (a->tile_cols < 0 || (a->tile_cols > 0 && (a->tile_cols % 4 || a->tile_cols < 4 ||
-                                                   a->tile_cols > 4 * dl::kMaxChunks ||
-                                                   (a->tile_cols & (a->tile_cols - 1)))))
-        return fail(DL_ERR_INVALID, "dl_mix_round: tile_cols must be 0 or a power of two in [4, %d]",
-                    4 * dl::kMaxChunks);
-    const bool tiled = a->tile_cols > 0;
-    if (!tiled && (a->ldx < a->n_params || a->ldy < a->n_params))
-        return fail(DL_ERR_INVALID, "dl_mix_round: ldx/ldy smaller than n_params");
-    if (!tiled && a->g && a->ldg < a->n_params)
-        return fail(DL_ERR_INVALID, "dl_mix_round: ldg < n_params");
-    // column-tiled: ld* = rows of each operand's tiled blocks (0 = the operand's own rows)
-    if (tiled && (a->ldx < 0 || a->ldy < 0 || a->ldg < 0 || (a->ldx > 0 && a->ldx < NL) ||
-                  (a->ldy > 0 && a->ldy < W.n_rows) || (a->g && a->ldg > 0 && a->ldg < NL) ||
-                  a->ldx > 65535 * 4 || a->ldy > 65535 * 4 || a->ldg > 65535 * 4))
-        return fail(DL_ERR_INVALID, "dl_mix_round: tiled ldx/ldg (>= n_local_src) or ldy (>= "
-                                    "n_rows) out of range");
-    if (a->n_halo > 0 && !a->halo)
-        return fail(DL_ERR_INVALID, "dl_mix_round: n_halo > 0 needs a halo buffer");
-    if (!tiled && a->n_halo > 0 && a->ldh < a->n_params)
-        return fail(DL_ERR_INVALID, "dl_mix_round: n_halo > 0 needs halo with ldh >= n_params");
-    if (!tiled && a->n_halo_blocks != 0)
-        return fail(DL_ERR_INVALID, "dl_mix_round: n_halo_blocks is for the column-tiled layout");
-    if (tiled && a->n_halo > 0) {
-        if (a->n_halo_blocks < 0 || a->n_halo_blocks > dl::kMaxHaloBlocks ||
-            (a->n_halo_blocks > 0 && !a->halo_block_rows))
-            return fail(DL_ERR_INVALID, "dl_mix_round: n_halo_blocks must be 0..%d with "
-                                        "halo_block_rows", dl::kMaxHaloBlocks);
-        int64_t sum = 0;
-        for (int b = 0; b < a->n_halo_blocks; ++b) {
-            if (a->halo_block_rows[b] <= 0)
-                return fail(DL_ERR_INVALID, "dl_mix_round: halo_block_rows[%d] <= 0", b);
-            sum += a->halo_block_rows[b];
-        }
-        if (a->n_halo_blocks > 0 && sum != a->n_halo)
-            return fail(DL_ERR_INVALID, "dl_mix_round: halo_block_rows sum to %lld, n_halo %d",
-                        (long long)sum, a->n_halo);
-        const int64_t ntl = (a->n_params + a->tile_cols - 1) / a->tile_cols;
-        if (ntl * a->n_halo * a->tile_cols * 4 >= ((int64_t)1 << 32))
-            return fail(DL_ERR_INVALID, "dl_mix_round: the tiled halo must span < 4 GiB");
-    }
-    // a column-tiled partition round reads mean_prev / colsum_out a float4 per chunk, tiles whole
-    if (tiled && (a->n_halo > 0 || part) && a->n_params % a->tile_cols)
-        return fail(DL_ERR_INVALID, "dl_mix_round: a column-tiled partition round needs "
-                                    "n_params %% tile_cols == 0");
-    if (W.uniform_row_nnz < 0 ||
-        (W.uniform_row_nnz > 0 && (int64_t)W.uniform_row_nnz * W.n_rows != W.nnz))
-        return fail(DL_ERR_INVALID, "dl_mix_round: uniform_row_nnz * n_rows != nnz");
-    if (W.shared_row_weights && W.uniform_row_nnz <= 0)
-        return fail(DL_ERR_INVALID, "dl_mix_round: shared_row_weights needs uniform_row_nnz > 0");
-    if (W.min_row_nnz < 0 || (int64_t)W.min_row_nnz * W.n_rows > W.nnz)
-        return fail(DL_ERR_INVALID, "dl_mix_round: min_row_nnz * n_rows > nnz");
-    const bool halo_round = a->n_halo > 0 || part;
-    if ((a->mean_prev || a->colsum_out) && !halo_round)
-        return fail(DL_ERR_INVALID, "dl_mix_round: mean_prev / colsum_out are for halo rounds "
-                                    "(n_halo > 0 or n_local_src != n_rows); local rounds fuse "
-                                    "the exact deviation");
-    if (a->mean && halo_round)
-        return fail(DL_ERR_INVALID, "dl_mix_round: the column mean of a halo round is global: "
-                                    "use colsum_out and an all-reduce");
-    if ((a->dev_sq || a->dev_max || a->mean_prev || a->colsum_out) && halo_round &&
-        !(a->mean_prev && a->colsum_out))
-        return fail(DL_ERR_INVALID,
-                    "dl_mix_round: a halo round's deviation is the lagged one: mean_prev, "
-                    "colsum_out and dev_sq together, or both without dev_sq (partial rows left "
-                    "in the workspace), or dl_column_sum + dl_deviation after it");
-    if (halo_round && a->mean_prev && !a->dev_sq && a->tile_cols <= 0)
-        return fail(DL_ERR_INVALID, "dl_mix_round: partial rows without dev_sq need the "
-                                    "column-tiled layout (one launch, plan grid rows)");
-    if (halo_round && a->mean_prev && !a->dev_sq && !a->partial_rows_out)
-        return fail(DL_ERR_INVALID, "dl_mix_round: a lagged halo round without dev_sq leaves its "
-                                    "deviation as partial rows: pass partial_rows_out (ABI 9) to "
-                                    "receive their count, or dev_sq for the reduced deviation");
-    // extents: a tiled operand of `rows` used rows inside blocks of `ld` rows spans (tiles - 1)
-    // block strides plus its used rows of the last tile
-    const int64_t Tc = a->tile_cols;
-    const int64_t ntl = tiled ? (a->n_params + Tc - 1) / Tc : 0;
-    auto tiled_b = [&](int64_t ld, int64_t rows) {
-        return (size_t)(((ntl - 1) * ld + rows) * Tc * 4);
-    };
-    const size_t xb = tiled ? tiled_b(a->ldx ? a->ldx : NL, NL)
-                            : ((size_t)(NL - 1) * a->ldx + a->n_params) * 4;
-    const size_t yb = tiled ? tiled_b(a->ldy ? a->ldy : W.n_rows, W.n_rows)
-                            : ((size_t)(W.n_rows - 1) * a->ldy + a->n_params) * 4;
-    if (overlaps(a->x, xb, a->y, yb)) return fail(DL_ERR_INVALID, "dl_mix_round: y overlaps x");
-    if (a->g) {
-        const size_t gb = tiled ? tiled_b(a->ldg ? a->ldg : NL, NL)
-                                : ((size_t)(NL - 1) * a->ldg + a->n_params) * 4;
-        if (overlaps(a->g, gb, a->y, yb)) return fail(DL_ERR_INVALID, "dl_mix_round: y overlaps g");
-    }
-    if (a->n_halo > 0) {
-        const size_t hb = tiled ? (size_t)(ntl * a->n_halo * Tc * 4)
-                                : ((size_t)(a->n_halo - 1) * a->ldh + a->n_params) * 4;
-        if (overlaps(a->halo, hb, a->y, yb))
-            return fail(DL_ERR_INVALID, "dl_mix_round: y overlaps halo");
-    }
-    return DL_OK;
-}
-
-dl::TileArgs tile_args(const dl_mix_args *a) {
-    dl::TileArgs t{};
-    t.x = a->x;
-    t.ldx = a->ldx;
-    t.halo = a->halo;
-    t.ldh = a->ldh;
-    t.g = a->g;
-    t.ldg = a->ldg;
-    t.y = a->y;
-    t.ldy = a->ldy;
-    t.rowptr = a->W.row_ptr;
-    t.col = a->W.col;
-    t.w = a->W.w;
-    t.n_rows = a->W.n_rows;
-    t.n_loc = local_src(a);
-    t.n_src = t.n_loc + a->n_halo;
-    t.nnz = a->W.nnz;
-    t.regular = a->W.uniform_row_nnz;
-    t.n_w = (a->W.uniform_row_nnz > 0 && a->W.shared_row_weights) ? a->W.uniform_row_nnz
-                                                                   : a->W.nnz;
-    t.mean_from_inputs = (a->W.doubly_stochastic && t.n_src == t.n_rows) ? 1 : 0;
-    {
-        // X, G and X' are streamed exactly once per round: non-temporal loads and stores keep
-        // them out of L2/MALL (measured +1.5 % on c2).  An X' that fits the 256-MB MALL is
-        // stored plainly instead, so the next kernel's reads of it (the c3 gradient launch
-        // reading X' as its parameters) can hit there: c3 +2 % steps/s (3743 vs 3668) -- but
-        // not in a partitioned round, whose next launch is the next column chunk's pack and mix
-        // (other columns): plain stores there left the following launch 16 % slower (one rank
-        // of 8, two chunks of 256 MB: 421.7 against 383.5-387.5 us a round with them
-        // non-temporal, profiles/r13/c4rank_env/).  DLAMD_NT_STORE=0/1 and DLAMD_NT_LOAD=0
-        // force them.
-        const char *nt = getenv("DLAMD_NT_STORE");
-        const size_t y_bytes = (size_t)a->W.n_rows * (size_t)a->n_params * 4;
-        const bool partitioned = a->n_halo > 0 || (a->n_local_src && a->n_local_src != a->W.n_rows);
-        t.nt_store = nt ? (nt[0] == '0' ? 0 : 1) : (y_bytes > kMallBytes || partitioned ? 1 : 0);
-        const char *ntl = getenv("DLAMD_NT_LOAD");
-        t.nt_load = !ntl ? 3 : ntl[0] == '0' ? 0 : ntl[0] == 'x' ? 1 : ntl[0] == 'g' ? 2 : 3;
-    }
-    t.n_params = a->n_params;
-    t.lr = a->lr;
-    // float4 access: every operand given 16-byte aligned, and row-major rows too (ld % 4)
-    bool vec = aligned16(a->x) && aligned16(a->y) && aligned16(a->g) && aligned16(a->halo) &&
-               aligned16(a->mean) && aligned16(a->mean_prev) && aligned16(a->colsum_out);
-    if (a->tile_cols <= 0)
-        vec = vec && a->ldx % 4 == 0 && a->ldy % 4 == 0 && (!a->g || a->ldg % 4 == 0) &&
-              (!a->halo || a->ldh % 4 == 0);
-    t.mean_prev = a->mean_prev;
-    t.colsum_out = a->colsum_out;
-    // the float4 kernel addresses rows with 32-bit byte offsets from the tile base
-    const int64_t lim = (int64_t)1 << 32;
-    const int64_t R = t.n_loc > t.n_rows ? t.n_loc : t.n_rows;
-    if (a->tile_cols > 0) {
-        t.tiled = 1;
-        // per-peer halo blocks (check_mix_args: <= kMaxHaloBlocks, rows summing to n_halo,
-        // the whole halo < 4 GiB)
-        const int64_t Tc = a->tile_cols;
-        const int64_t ntl = (a->n_params + Tc - 1) / Tc;
-        const int nb = a->n_halo > 0 ? (a->n_halo_blocks > 0 ? a->n_halo_blocks : 1) : 0;
-        t.n_hblk = nb;
-        int32_t r0 = 0;
-        for (int b = 0; b < nb; ++b) {
-            t.hblk_row0[b] = r0;
-            t.hblk_off[b] = (uint32_t)(ntl * r0 * Tc * 4);
-            r0 += a->n_halo_blocks > 0 ? a->halo_block_rows[b] : a->n_halo;
-        }
-        t.hblk_row0[nb] = r0;
-    } else if (((R - 1) * a->ldx + 128) * 4 >= lim || ((R - 1) * a->ldy + 128) * 4 >= lim ||
-               (a->g && ((R - 1) * a->ldg + 128) * 4 >= lim) ||
-               // a halo row's offset (row and column) is one 32-bit value
-               (a->n_halo > 0 && (int64_t)a->n_halo * a->ldh * 4 >= lim)) {
-        vec = false;
-    }
-    t.vec = vec ? 1 : 0;
-    t.mean = a->mean;
-    return t;
-}
-
-// FAST-path strides (TileArgs) for tiles of T columns; a column-tiled operand's tile stride is
-// its block rows (ld*, 0 = its own rows) x T floats
-void set_tile_strides(dl::TileArgs &t, const dl_mix_args *a, int64_t T) {
-    if (t.tiled) {
-        t.xts = (a->ldx ? a->ldx : (int64_t)t.n_loc) * T * 4;
-        t.gts = (a->ldg ? a->ldg : (int64_t)t.n_loc) * T * 4;
-        t.yts = (a->ldy ? a->ldy : (int64_t)t.n_rows) * T * 4;
-        t.xrs = t.grs = t.yrs = (uint32_t)(T * 4);
-    } else {
-        t.xts = t.gts = t.yts = T * 4;
-        t.xrs = (uint32_t)(a->ldx * 4);
-        t.grs = (uint32_t)(a->ldg * 4);
-        t.yrs = (uint32_t)(a->ldy * 4);
-        t.hrs = (uint32_t)(a->ldh * 4);
-    }
+    char err[dl::kErrLen];
+    return status(dl::check_mix_args(a, err), err);
 }
 
 // Deviation of x (n_rows x n_params) via the two-pass path: mean (given or column mean), then
@@ -328,10 +118,77 @@ int zero_deviation(int32_t n_rows, float *dev_sq, float *dev_max, hipStream_t s)
     return DL_OK;
 }
 
+// Issues the launches a shaping function of launch.h described and the zeroing or reduce after
+// them (kAfterPartialRows and kAfterTwoPass are dl_mix_round's own).  tile: what a tile launch
+// is called in a HIP failure's text.
+int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, const char *tile,
+        hipStream_t s) {
+    for (int i = 0; i < L.n; ++i) {
+        const dl::Launch &l = L.l[i];
+        hipError_t e = hipErrorInvalidValue;
+        const char *who = "";
+        switch (l.kind) {
+            case dl::kLaunchTile:
+                e = dl::launch_mix_tile(l.t, l.chunks, l.sgd, l.dev, l.mix, l.grid, l.lds, l.fast,
+                                        s);
+                break;
+            case dl::kLaunchTileReg:
+                e = dl::launch_mix_tile_reg(l.t, l.chunks, l.head, l.tail_fmt, l.sgd, l.dev, l.grid,
+                                            l.lds, s);
+                break;
+            case dl::kLaunchGather:
+                e = dl::launch_mix_gather(l.t, l.sgd, l.columns, s);
+                who = "mix_gather_kernel launch";
+                break;
+            case dl::kLaunchMulti:
+                e = dl::launch_mix_multi(l.t, l.chunks, l.rounds, l.sgd, l.dev, l.grid, l.lds, s);
+                who = "mix_multi_kernel launch";
+                break;
+            case dl::kLaunchTrace:
+                e = dl::launch_mix_trace(l.t, l.chunks, l.planes, l.rounds, l.grid, l.lds, trace,
+                                         s);
+                who = "mix_trace_kernel launch";
+                break;
+            case dl::kLaunchTraceIrr:
+                e = dl::launch_mix_trace_irr(l.t, l.head, l.gm, l.narrow, l.rounds, l.grid, l.lds,
+                                             trace, s);
+                who = "mix_trace_kernel launch";
+                break;
+        }
+        if (e == hipSuccess) continue;
+        if (*who) return hip_fail(e, who);
+        return fail(DL_ERR_HIP, "%s%s launch: %s (%d)", tile, l.fast ? "" : " (tail)",
+                    hipGetErrorString(e), (int)e);
+    }
+    if (L.after == dl::kAfterZero) return zero_deviation(L.l[0].t.n_rows, dev_sq, dev_max, s);
+    if (L.after == dl::kAfterReduce) {
+        hipError_t e = dl::launch_dev_reduce(L.partial, L.parts, L.rows, dev_sq, dev_max, s,
+                                             L.max_zeroed);
+        if (e != hipSuccess) return hip_fail(e, "dev_reduce launch");
+    }
+    return DL_OK;
+}
+
+// The one-pass deviation (launch.h shape_deviation); DL_ERR_UNSUPPORTED without launching when
+// the agents do not fit one tile.
+int deviation_one_pass(const float *x, int64_t ldx, int32_t tile_cols, int32_t n_rows,
+                       int64_t n_params, float *dev_sq, float *dev_max, float *mean_out,
+                       char *ws, size_t ws_bytes, hipStream_t s) {
+    dl::Launches L;
+    char err[dl::kErrLen] = "";
+    const int rc = dl::shape_deviation(x, ldx, tile_cols, n_rows, n_params, mean_out, device_cus(),
+                                       ws, ws_bytes, &L, err);
+    if (rc) return *err ? status(rc, err) : rc;
+    return run(L, dev_sq, dev_max, nullptr, "dev tile", s);
+}
+
 }  // namespace
 
 namespace dl {
-int fail_msg(int code, const char *msg) { return fail(code, "%s", msg); }
+int fail_msg(int code, const char *msg) {
+    g_err = msg;
+    return code;
+}
 }  // namespace dl
 
 extern "C" {
@@ -343,7 +200,7 @@ int dl_mix_trace_plan(const dl_mix_args *args, int32_t *max_rounds) {
     if (!max_rounds) return fail(DL_ERR_INVALID, "dl_mix_trace_plan: max_rounds is NULL");
     int rc = check_mix_args(args);
     if (rc) return rc;
-    TracePlan tp;
+    dl::TracePlan tp;
     rc = plan_with(dl::plan_trace, args, dl::read_knobs(), &tp);
     if (rc) return rc;
     *max_rounds = tp.max_rounds;
@@ -361,40 +218,12 @@ int dl_mix_rounds_trace(const dl_mix_args *args, int32_t rounds, float *trace, v
     int rc = check_mix_args(args);
     if (rc) return rc;
     if (!trace) return fail(DL_ERR_INVALID, "dl_mix_rounds_trace: trace is NULL");
-    const dl::Knobs knobs = dl::read_knobs();
-    TracePlan tp;
-    rc = plan_with(dl::plan_trace, args, knobs, &tp);
-    if (rc) return rc;
-    if (rounds < 1 || rounds > tp.max_rounds)
-        return fail(DL_ERR_INVALID, "dl_mix_rounds_trace: rounds must be in [1, %d] (one "
-                                    "traced pass), got %d", tp.max_rounds, rounds);
-    dl::TileArgs t = tile_args(args);
-    if (!t.vec)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: operands must be 16-byte aligned "
-                                        "float4 rows");
-    const int32_t N = args->W.n_rows;
-    if (tp.irr && t.tiled && args->tile_cols % 4)
-        return fail(DL_ERR_INVALID, "dl_mix_rounds_trace: tile_cols must be a multiple of 4");
-    // a step walks float4 chunks: of an operand tile when column-tiled, else of the row itself
-    t.lchunks = t.tiled ? args->tile_cols / 4 : 1;
-    set_tile_strides(t, args, t.tiled ? args->tile_cols : 4);
-    t.n_tiles = (int32_t)tp.n_steps;
-    t.csr_off = tp.csr_off;
-    t.scratch_off = tp.scratch_off;
-    const size_t need = align_up((size_t)tp.grid * rounds * N * 4);
-    char *ws = static_cast<char *>(workspace);
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u) || ws_bytes < need)
-        return fail(DL_ERR_WORKSPACE, "dl_mix_rounds_trace: needs a 16-byte aligned workspace "
-                                      "of %zu bytes (dl_mix_trace_workspace_bytes)", need);
-    t.dev_partial = reinterpret_cast<float *>(ws);
-    hipError_t e = tp.irr ? dl::launch_mix_trace_irr(t, tp.head, tp.gm != 0, tp.narrow != 0,
-                                                      rounds, tp.grid,
-                                                      (int)tp.lds, trace,
-                                                      static_cast<hipStream_t>(stream))
-                          : dl::launch_mix_trace(t, tp.chunks, knobs.trace_planes, rounds, tp.grid,
-                                                 (int)tp.lds, trace,
-                                                 static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? DL_OK : hip_fail(e, "mix_trace_kernel launch");
+    dl::Launches L;
+    char err[dl::kErrLen];
+    rc = dl::shape_trace(*args, rounds, device_cus(), dl::read_knobs(), workspace, ws_bytes, &L,
+                         err);
+    if (rc) return status(rc, err);
+    return run(L, nullptr, nullptr, trace, "", static_cast<hipStream_t>(stream));
 }
 
 int dl_mix_rounds_plan(const dl_mix_args *args, dl_mix_plan *plan) {
@@ -414,40 +243,12 @@ int dl_mix_rounds(const dl_mix_args *args, int32_t rounds, void *workspace, size
     g_err.clear();
     int rc = check_mix_args(args);
     if (rc) return rc;
-    if (rounds < 1) return fail(DL_ERR_INVALID, "dl_mix_rounds: rounds must be >= 1");
-    Plan pl;
-    rc = plan_rounds(args, &pl);
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int32_t Nr = args->W.n_rows;
-    dl::TileArgs t = tile_args(args);
-    if (!t.vec)
-        return fail(DL_ERR_UNSUPPORTED, "dl_mix_rounds: operands must be 16-byte aligned float4 "
-                                        "rows");
-    set_tile_strides(t, args, pl.pub.tile_cols);
-    t.n_tiles = pl.pub.n_tiles;
-    t.col_base = 0;
-    t.csr_off = pl.csr_off;
-    t.scratch_off = pl.scratch_off;
-    char *ws = static_cast<char *>(workspace);
-    if (pl.dev) {
-        const size_t need = align_up((size_t)pl.pub.grid * Nr * 4);
-        if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u) || ws_bytes < need)
-            return fail(DL_ERR_WORKSPACE, "dl_mix_rounds: deviation outputs need a 16-byte "
-                                          "aligned workspace of %zu bytes", need);
-        t.dev_partial = reinterpret_cast<float *>(ws);
-        t.dev_max_zero = reinterpret_cast<unsigned int *>(args->dev_max);
-    }
-    hipError_t e = dl::launch_mix_multi(t, pl.chunks, rounds, args->g != nullptr, pl.dev,
-                                        pl.pub.grid, pl.pub.lds_bytes, s);
-    if (e != hipSuccess) return hip_fail(e, "mix_multi_kernel launch");
-    if (pl.dev) {
-        if (Nr <= 1) return zero_deviation(Nr, args->dev_sq, args->dev_max, s);
-        e = dl::launch_dev_reduce(t.dev_partial, pl.pub.grid, Nr, args->dev_sq, args->dev_max, s,
-                                  true);
-        if (e != hipSuccess) return hip_fail(e, "dev_reduce launch");
-    }
-    return DL_OK;
+    dl::Launches L;
+    char err[dl::kErrLen];
+    rc = dl::shape_rounds(*args, rounds, device_cus(), dl::read_knobs(), workspace, ws_bytes, &L,
+                          err);
+    if (rc) return status(rc, err);
+    return run(L, args->dev_sq, args->dev_max, nullptr, "", static_cast<hipStream_t>(stream));
 }
 
 int dl_mix_until_fits(int32_t n_rows, int64_t n_params, int32_t nnz) {
@@ -638,197 +439,24 @@ int dl_mix_round(const dl_mix_args *args, void *workspace, size_t ws_bytes, dl_s
     int rc = check_mix_args(args);
     if (rc) return rc;
     if (args->partial_rows_out) *args->partial_rows_out = 0;
-    Plan pl;
-    rc = plan_mix(args, &pl);
-    if (rc) return rc;
+    dl::Launches L;
+    char err[dl::kErrLen];
+    rc = dl::shape_round(*args, device_cus(), dl::read_knobs(), workspace, ws_bytes, &L, err);
+    if (rc) return status(rc, err);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int32_t Nr = args->W.n_rows;
-    char *ws = static_cast<char *>(workspace);
-    dl::TileArgs t = tile_args(args);
-    // halo rounds with the lagged deviation: partials only when the deviation of x is asked for
-    const bool lag = dl::tile_lag(t);
-    const bool parts = pl.dev;   // a lagged halo round always writes its deviation partials
-    const int32_t Np = lag ? t.n_loc : Nr;   // partial rows: lagged = one per local source row
-    if (parts && (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u)))
-        return fail(DL_ERR_WORKSPACE, "dl_mix_round: deviation outputs need a 16-byte aligned "
-                                      "workspace of dl_mix_workspace_bytes()");
-    const bool sgd = args->g != nullptr;
-    if ((pl.pub.path == 4 || pl.pub.path == 5) && !t.vec) {   // register-CSR: FAST-only
-        // the gather kernel reads row-major operands only: column-tiled ones are refused as on
-        // path 1, row-major ones take the gather path
-        if (t.tiled)
-            return fail(DL_ERR_INVALID, "dl_mix_round: tiled operands must be 16-byte aligned");
-        pl.pub.path = 2;
-    }
-    if (pl.pub.path == 1 || pl.pub.path == 4 || pl.pub.path == 5) {
-        // full tiles on the branch-free float4 kernel, the ragged tail tile (and unaligned
-        // operands) on the guarded one; each launch writes its own deviation partial rows
-        const bool reg_csr = pl.pub.path == 4 || pl.pub.path == 5;
-        const int64_t T = pl.pub.tile_cols;
-        if (t.tiled && !t.vec)
-            return fail(DL_ERR_INVALID, "dl_mix_round: tiled operands must be 16-byte aligned");
-        set_tile_strides(t, args, T);
-        const int64_t n_full = t.tiled ? pl.pub.n_tiles : (t.vec ? args->n_params / T : 0);
-        const int64_t n_tail = pl.pub.n_tiles - n_full;  // 0 or 1 when vec, else all tiles
-        int grid_full = (int)(n_full < pl.pub.grid ? n_full : pl.pub.grid);
-        int grid_tail = (int)(n_tail < pl.pub.grid ? n_tail : pl.pub.grid);
-        const size_t need = align_up((size_t)(grid_full + grid_tail) * Np * 4);
-        if (parts && ws_bytes < need)
-            return fail(DL_ERR_WORKSPACE, "dl_mix_round: workspace %zu < %zu bytes", ws_bytes, need);
-        t.csr_off = pl.csr_off;
-        t.scratch_off = pl.scratch_off;
-        if (pl.grp > 1) {   // tile groups: chunk c of a kernel row -> data tile c / (T / 4)
-            t.grp = pl.grp;
-            t.cd_sh = __builtin_ctz((unsigned)(T / 4));
-        }
-        float *partial = parts ? reinterpret_cast<float *>(ws) : nullptr;
-        if (parts) t.dev_max_zero = reinterpret_cast<unsigned int *>(args->dev_max);
-        int lds = pl.pub.lds_bytes;
-        if (const char *v = getenv("DLAMD_LDS_MIN")) {  // measurement knob: LDS per workgroup
-            const int m = atoi(v);                        // bounds workgroups per CU
-            if (m > lds) lds = m < (int)dl::kLdsBytes ? m : (int)dl::kLdsBytes;
-        }
-        if (pl.pub.path == 5 && pl.head < 5 && args->n_hub_rows > 0) {
-            // hub rows' register heads behind the LDS tail: as many as fit, <= 256
-            const int hb = pl.head * 8;
-            const int room = ((int)dl::kLdsBytes - lds) / hb;
-            int nh = args->n_hub_rows < 256 ? args->n_hub_rows : 256;
-            if (nh > Nr) nh = Nr;
-            if (nh > room) nh = room;
-            if (nh > 0) {
-                t.n_hub = nh;
-                t.hub_off = (uint32_t)((lds + 15) & ~15);
-                lds = (int)t.hub_off + nh * hb;
-                if (lds > (int)dl::kLdsBytes) {   // (alignment) fall back to no hub lanes
-                    t.n_hub = 0;
-                    lds = pl.pub.lds_bytes;
-                }
-            }
-        }
-        if (grid_full > 0) {
-            t.n_tiles = (int32_t)n_full;
-            t.col_base = 0;
-            // row-major operands: each workgroup walks one contiguous run of tiles instead of
-            // every grid-th tile, so its row segments follow each other in every row (c3's
-            // 256 x 164,608 round: 103.8 against 105.3-107.3 us between events,
-            // profiles/r13/c3_env/); the column-tiled layout keeps the grid stride (+0.4 % with
-            // runs on c2, within noise).  DLAMD_TILE_RUN=0 / 1 forces it off / on.
-            const char *v = getenv("DLAMD_TILE_RUN");
-            const bool runs = v ? v[0] == '1' : !t.tiled;
-            if (runs) t.tile_run = (int32_t)((n_full + grid_full - 1) / grid_full);
-            t.dev_partial = partial;
-            hipError_t e = reg_csr ? dl::launch_mix_tile_reg(t, pl.chunks, pl.head, pl.tail_fmt,
-                                                             sgd, pl.dev, grid_full, lds, s)
-                                   : dl::launch_mix_tile(t, pl.chunks, sgd, pl.dev, true,
-                                                         grid_full, lds, true, s);
-            if (e != hipSuccess) return hip_fail(e, "mix_tile_kernel launch");
-        }
-        if (grid_tail > 0) {
-            if (reg_csr) return fail(DL_ERR_INVALID, "dl_mix_round: register-CSR plan with a tail");
-            t.n_tiles = (int32_t)n_tail;
-            t.col_base = n_full * T;
-            t.tile_run = 0;
-            t.dev_partial = parts ? partial + (size_t)grid_full * Np : nullptr;
-            hipError_t e = dl::launch_mix_tile(t, pl.chunks, sgd, pl.dev, true, grid_tail,
-                                               lds, false, s);
-            if (e != hipSuccess) return hip_fail(e, "mix_tile_kernel (tail) launch");
-        }
-        if (parts) {
-            if (Nr <= 1 && !lag) return zero_deviation(Nr, args->dev_sq, args->dev_max, s);
-            // a lagged round without dev_sq leaves its partial rows to the caller (column
-            // chunks reduced once, dl_row_sums) and says how many; its dev_max, if any, the
-            // kernel zeroed
-            if (lag && !args->dev_sq) {
-                *args->partial_rows_out = grid_full + grid_tail;
-                return DL_OK;
-            }
-            hipError_t e = dl::launch_dev_reduce(partial, grid_full + grid_tail, Np, args->dev_sq,
-                                                 args->dev_max, s, true);
-            if (e != hipSuccess) return hip_fail(e, "dev_reduce launch");
-        }
-        return DL_OK;
-    }
-    hipError_t e = dl::launch_mix_gather(t, sgd, s);
-    if (e != hipSuccess) return hip_fail(e, "mix_gather_kernel launch");
-    if (pl.dev) {
-        if (Nr <= 1) return zero_deviation(Nr, args->dev_sq, args->dev_max, s);
-        return deviation_two_pass(args->y, args->ldy, Nr, args->n_params, nullptr, args->dev_sq,
-                                  args->dev_max, args->mean, ws, ws_bytes, s);
-    }
+    rc = run(L, args->dev_sq, args->dev_max, nullptr, "mix_tile_kernel", s);
+    if (rc) return rc;
+    if (L.after == dl::kAfterPartialRows) *args->partial_rows_out = L.parts;
+    if (L.after == dl::kAfterTwoPass)
+        return deviation_two_pass(args->y, args->ldy, args->W.n_rows, args->n_params, nullptr,
+                                  args->dev_sq, args->dev_max, args->mean,
+                                  static_cast<char *>(workspace), ws_bytes, s);
     return DL_OK;
 }
 
 size_t dl_deviation_workspace_bytes(int32_t n_rows, int64_t n_params) {
     return dl_mix_workspace_bytes(n_rows, 0, n_params);
 }
-
-}  // extern "C"
-
-namespace {
-
-// One-pass deviation on the tile kernel (MIX = false): every agent of a column tile in one
-// workgroup, column mean in LDS scratch.  tile_cols > 0: x in the column-tiled layout.
-// Returns DL_ERR_UNSUPPORTED (without launching) when the agents do not fit one tile.
-int deviation_one_pass(const float *x, int64_t ldx, int32_t tile_cols, int32_t n_rows,
-                       int64_t n_params, float *dev_sq, float *dev_max, float *mean_out, char *ws,
-                       size_t ws_bytes, hipStream_t s) {
-    int c = tile_cols > 0 ? tile_cols / 4 : dl::next_pow2_chunks(n_params);
-    for (; c >= 1; c >>= 1) {
-        if ((int64_t)n_rows * c <= (int64_t)dl::kRowsPerThread * dl::kTileThreads) break;
-        if (tile_cols > 0) return DL_ERR_UNSUPPORTED;
-    }
-    if (c < 1) return DL_ERR_UNSUPPORTED;
-    const int lds = (dl::kTileThreads / 64) * c * 16;
-    const int64_t T = 4 * c;
-    bool vec = aligned16(x) && (!mean_out || aligned16(mean_out));
-    if (tile_cols == 0)
-        vec = vec && ldx % 4 == 0 && ((int64_t)(n_rows - 1) * ldx + 128) * 4 < ((int64_t)1 << 32);
-    else if (!vec)
-        return fail(DL_ERR_INVALID, "dl_deviation_tiled: x must be 16-byte aligned");
-    const int64_t n_tiles = (n_params + T - 1) / T;
-    const int64_t n_full = tile_cols > 0 ? n_tiles : (vec ? n_params / T : 0);
-    const int64_t n_tail = n_tiles - n_full;
-    const int64_t gmax = (int64_t)device_cus() * 2;
-    const int grid_full = (int)(n_full < gmax ? n_full : gmax);
-    const int grid_tail = (int)(n_tail < gmax ? n_tail : gmax);
-    if (ws_bytes < align_up((size_t)(grid_full + grid_tail) * n_rows * 4))
-        return fail(DL_ERR_WORKSPACE, "dl_deviation: workspace too small");
-    dl::TileArgs t{};
-    t.x = x;
-    t.ldx = ldx;
-    t.n_rows = n_rows;
-    t.n_src = n_rows;
-    t.n_loc = n_rows;
-    t.n_params = n_params;
-    t.vec = vec ? 1 : 0;
-    t.mean = mean_out;
-    t.tiled = tile_cols > 0 ? 1 : 0;
-    t.xts = tile_cols > 0 ? (int64_t)n_rows * T * 4 : T * 4;
-    t.xrs = (uint32_t)(tile_cols > 0 ? T * 4 : ldx * 4);
-    t.scratch_off = 0;
-    float *partial = reinterpret_cast<float *>(ws);
-    if (grid_full > 0) {
-        t.n_tiles = (int32_t)n_full;
-        t.col_base = 0;
-        t.dev_partial = partial;
-        hipError_t e = dl::launch_mix_tile(t, c, false, true, false, grid_full, lds, true, s);
-        if (e != hipSuccess) return hip_fail(e, "dev tile launch");
-    }
-    if (grid_tail > 0) {
-        t.n_tiles = (int32_t)n_tail;
-        t.col_base = n_full * T;
-        t.dev_partial = partial + (size_t)grid_full * n_rows;
-        hipError_t e = dl::launch_mix_tile(t, c, false, true, false, grid_tail, lds, false, s);
-        if (e != hipSuccess) return hip_fail(e, "dev tile (tail) launch");
-    }
-    hipError_t e = dl::launch_dev_reduce(partial, grid_full + grid_tail, n_rows, dev_sq, dev_max, s);
-    if (e != hipSuccess) return hip_fail(e, "dev_reduce launch");
-    return DL_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int dl_deviation(const float *x, int64_t ldx, int32_t n_rows, int64_t n_params,
                  const float *mean_in, float *dev_sq, float *dev_max, float *mean_out,
@@ -838,7 +466,7 @@ int dl_deviation(const float *x, int64_t ldx, int32_t n_rows, int64_t n_params,
     if (!x || n_rows <= 0 || n_params <= 0 || ldx < n_params)
         return fail(DL_ERR_INVALID, "dl_deviation: bad x/n_rows/n_params/ldx");
     char *ws = static_cast<char *>(workspace);
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u))
+    if (!dl::ws_holds(ws, ws_bytes, 0))
         return fail(DL_ERR_WORKSPACE, "dl_deviation: needs a 16-byte aligned workspace");
     if (n_rows <= 1) {
         if (mean_out) {
@@ -869,7 +497,7 @@ int dl_deviation_tiled(const float *x, int32_t n_rows, int64_t n_params, int32_t
         (tile_cols & (tile_cols - 1)))
         return fail(DL_ERR_INVALID, "dl_deviation_tiled: bad x/n_rows/n_params/tile_cols");
     char *ws = static_cast<char *>(workspace);
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u))
+    if (!dl::ws_holds(ws, ws_bytes, 0))
         return fail(DL_ERR_WORKSPACE, "dl_deviation_tiled: needs a 16-byte aligned workspace");
     if (n_rows <= 1) {
         if (mean_out) {

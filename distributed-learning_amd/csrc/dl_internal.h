@@ -5,90 +5,27 @@
 
 #include <cstdlib>
 
-#include "plan.h"   // tile geometry shared with the planner: k* constants, tile_kv, trace rounds
+#include "launch.h"   // TileArgs; plan.h: the tile geometry shared with the planner
 
 namespace dl {
-
-struct TileArgs {
-    const float *x;
-    int64_t ldx;
-    const float *halo;
-    int64_t ldh;
-    const float *g;
-    int64_t ldg;
-    float *y;
-    int64_t ldy;
-    const int32_t *rowptr;
-    const int32_t *col;
-    const float *w;
-    int32_t n_rows;   // output rows (local agents)
-    int32_t n_src;    // rows staged in LDS = n_loc + n_halo
-    int32_t n_loc;    // source rows read from x (and stepped with g); n_rows unless the round
-                      // mixes one row set of an agent partition from a wider local window
-    int32_t nnz;
-    int32_t regular;  // >0: every row has exactly `regular` entries (row_ptr not staged)
-    int32_t n_w;      // weights staged in LDS: nnz, or `regular` when every row shares row 0's
-    int32_t mean_from_inputs;  // 1: W doubly stochastic -> tile mean taken from the staged t
-    int32_t nt_store;          // 1: non-temporal stores of y (FAST path)
-    int32_t nt_load;           // non-temporal loads (FAST path): bit 0 x / halo, bit 1 g
-    int64_t n_params;
-    int32_t n_tiles;
-    int64_t col_base; // first column of tile 0
-    float lr;
-    int32_t vec;      // 1: x/g/y/halo 16-byte aligned and ld % 4 == 0
-    uint32_t csr_off; // byte offset of the staged CSR in LDS
-    uint32_t scratch_off; // byte offset of the 16 x C float4 mean scratch in LDS
-    // FAST-path strides in bytes: tile stride (next tile's row 0) and row stride.
-    //   row-major:      xts = T*4,          xrs = ldx*4   (tile base also offset by col_base)
-    //   column-tiled:   xts = n_rows*T*4,   xrs = T*4     (block [n_rows][T] per tile)
-    int32_t tiled;
-    int64_t xts, gts, yts;
-    uint32_t xrs, grs, yrs;
-    uint32_t hrs;     // halo row stride in bytes (ldh*4)
-    int32_t lchunks;     // mix_trace_kernel: float4 chunks per operand tile (1 = row-major)
-    float *dev_partial;  // [gridDim.x][n_rows] per-workgroup partial ||y_a - mean||^2
-                         // (lagged halo deviation: [gridDim.x][n_loc], one per source row)
-    float *mean;         // [n_params] nullable
-    unsigned int *dev_max_zero;  // nullable: workgroup 0 zeroes it (dev_reduce's atomicMax target,
-                                 // so that launch needs no memset of its own)
-    const float *mean_prev;      // halo rounds: global column mean of x (lagged deviation)
-    float *colsum_out;           // halo rounds: this rank's column sums of y
-    // column-tiled halo (tiled != 0, n_src > n_loc): n_hblk per-peer blocks back to back; block
-    // b holds halo rows [hblk_row0[b], hblk_row0[b + 1]) as [n_tiles][rows_b][T], starting
-    // hblk_off[b] bytes into `halo`
-    int32_t n_hblk;
-    int32_t hblk_row0[17];
-    uint32_t hblk_off[16];
-    // path 5: rows [0, n_hub) folded by four column lanes each; their register heads as
-    // {weight, row} pairs at LDS byte offset hub_off
-    int32_t n_hub;
-    uint32_t hub_off;
-    // column-tiled partition rounds (FAST): one kernel tile = `grp` consecutive data tiles of T
-    // columns (chunk c of a kernel row is chunk c & (2^cd_sh - 1) of data tile c >> cd_sh), so a
-    // short launch moves grp times the bytes per pass; grp = 1 (the default) is the plain tile
-    int32_t grp;
-    int32_t cd_sh;
-    int32_t tile_run;          // 0: workgroup b walks tiles b, b + grid, ...; > 0: the run
-                               // [b * tile_run, (b + 1) * tile_run) (DLAMD_TILE_RUN, a knob)
-};
-constexpr int kMaxHaloBlocks = 16;
 
 // Raise kernel k's dynamic-LDS limit to the whole CU (kLdsBytes), once per (kernel, device):
 // launches then make no attribute call, so they are capturable in a hipGraph and carry no
 // per-launch driver work.
 hipError_t allow_full_lds(const void *k);
+// Launch kernel k on `grid` workgroups of kTileThreads with `lds` bytes of dynamic LDS.
+template <class... P, class... A>
+hipError_t launch_lds(void (*k)(P...), int grid, int lds, hipStream_t s, const A &...args) {
+    hipError_t e = allow_full_lds(reinterpret_cast<const void *>(k));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kTileThreads), lds, s, args...);
+    return hipGetLastError();
+}
 
 hipError_t launch_mix_tile(const TileArgs &a, int chunks, bool sgd, bool dev, bool mix, int grid,
                            int lds_bytes, bool fast, hipStream_t s);
-// true when a launch of this plan runs the halo instantiation with the lagged deviation
-// a round of an agent partition: halo source rows, or output rows that are not the source rows
-inline bool tile_partitioned(const TileArgs &a) {
-    return a.n_src != a.n_rows || a.n_loc != a.n_rows;
-}
-inline bool tile_lag(const TileArgs &a) {
-    return tile_partitioned(a) && (a.mean_prev != nullptr || a.colsum_out != nullptr);
-}
-hipError_t launch_mix_gather(const TileArgs &a, bool sgd, hipStream_t s);
+// columns: Knobs::gather_order_columns
+hipError_t launch_mix_gather(const TileArgs &a, bool sgd, bool columns, hipStream_t s);
 // The register-CSR tile kernels (plan.h reg_csr_supported / reg_tail_supported).  head 0: the
 // regular one (path 4); head > 0: head + LDS tail (path 5), the tail as {weight, row} pairs of
 // 8 B (tail_fmt 2, heads < 5) or weights + u16 rows (1: 6 B)

@@ -1,0 +1,498 @@
+// Launch shaping (launch.h): argument validation, the kernels' TileArgs, and what every round
+// entry point launches.
+#include "launch.h"
+
+#include <cstring>
+
+namespace dl {
+
+namespace {
+
+// MI355X Infinity Cache (MALL), shared by all XCDs
+constexpr size_t kMallBytes = (size_t)256 << 20;
+
+// FAST-path strides of one operand for tiles of T columns; a column-tiled operand's tile stride
+// is its block rows (ld, 0 = its own rows) x T floats
+void tile_stride(bool tiled, int64_t ld, int64_t rows, int64_t T, int64_t *ts, uint32_t *rs) {
+    *ts = tiled ? (ld ? ld : rows) * T * 4 : T * 4;
+    *rs = (uint32_t)(tiled ? T * 4 : ld * 4);
+}
+void set_tile_strides(TileArgs &t, int64_t T) {
+    tile_stride(t.tiled, t.ldx, t.n_loc, T, &t.xts, &t.xrs);
+    tile_stride(t.tiled, t.ldg, t.n_loc, T, &t.gts, &t.grs);
+    tile_stride(t.tiled, t.ldy, t.n_rows, T, &t.yts, &t.yrs);
+    if (!t.tiled) t.hrs = (uint32_t)(t.ldh * 4);
+}
+
+// Full tiles on the branch-free float4 kernel, the ragged tail tile (and unaligned operands) on
+// the guarded one, each on at most gmax workgroups.
+struct Split {
+    int64_t n_full, n_tail;  // n_tail: 0 or 1 when vec, else all tiles
+    int grid_full, grid_tail;
+    int parts() const { return grid_full + grid_tail; }
+};
+Split split_tiles(const TileArgs &t, int64_t T, int64_t n_tiles, int64_t gmax) {
+    Split s;
+    s.n_full = t.tiled ? n_tiles : (t.vec ? t.n_params / T : 0);
+    s.n_tail = n_tiles - s.n_full;
+    s.grid_full = (int)(s.n_full < gmax ? s.n_full : gmax);
+    s.grid_tail = (int)(s.n_tail < gmax ? s.n_tail : gmax);
+    return s;
+}
+// The tile launches of a split from the prototype in out->l[0]; each writes its own deviation
+// partial rows ([grid][part_rows] floats at `partial`, the tail's behind the full tiles').
+// runs: the full launch's workgroups walk contiguous runs of tiles.
+void push_split(Launches *out, const Split &s, int64_t T, float *partial, int32_t part_rows,
+                bool runs) {
+    Launch &full = out->l[0];
+    if (s.grid_tail > 0) {
+        Launch &tail = out->l[s.grid_full > 0 ? 1 : 0];
+        if (s.grid_full > 0) tail = full;
+        tail.kind = kLaunchTile;
+        tail.fast = false;
+        tail.grid = s.grid_tail;
+        tail.t.n_tiles = (int32_t)s.n_tail;
+        tail.t.col_base = s.n_full * T;
+        tail.t.dev_partial = partial ? partial + (size_t)s.grid_full * part_rows : nullptr;
+    }
+    if (s.grid_full > 0) {
+        full.fast = true;
+        full.grid = s.grid_full;
+        full.t.n_tiles = (int32_t)s.n_full;
+        if (runs) full.t.tile_run = (int32_t)((s.n_full + s.grid_full - 1) / s.grid_full);
+        full.t.dev_partial = partial;
+    }
+    out->n = (s.grid_full > 0) + (s.grid_tail > 0);
+}
+
+// an empty list whose first launch is zeroed (the second is a copy of it when there is one)
+void reset(Launches *out) {
+    out->n = 0;
+    out->after = kAfterNothing;
+    out->partial = nullptr;
+    out->parts = out->rows = 0;
+    out->max_zeroed = false;
+    std::memset(&out->l[0], 0, sizeof out->l[0]);
+}
+
+void after_reduce(Launches *out, const float *partial, int parts, int rows, bool max_zeroed) {
+    out->after = kAfterReduce;
+    out->partial = partial;
+    out->parts = parts;
+    out->rows = rows;
+    out->max_zeroed = max_zeroed;
+}
+
+}  // namespace
+
+int check_mix_args(const dl_mix_args *a, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_mix_round: args is NULL");
+    const dl_csr &W = a->W;
+    if (W.n_rows <= 0)
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: n_rows must be > 0 (got %d)", W.n_rows);
+    if (a->n_params <= 0) return fail(err, DL_ERR_INVALID, "dl_mix_round: n_params must be > 0");
+    if (a->n_halo < 0) return fail(err, DL_ERR_INVALID, "dl_mix_round: n_halo < 0");
+    if (a->n_local_src < 0) return fail(err, DL_ERR_INVALID, "dl_mix_round: n_local_src < 0");
+    const int32_t NL = local_src(*a);
+    // an interior / boundary row set of an agent partition (outputs need not be source rows)
+    const bool part = mix_partitioned(*a);
+    if ((int64_t)W.n_rows > (int64_t)NL + a->n_halo)
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: n_rows %d > n_local_src + n_halo %lld",
+                    W.n_rows, (long long)NL + a->n_halo);
+    if (W.nnz < 0) return fail(err, DL_ERR_INVALID, "dl_mix_round: nnz < 0");
+    if (a->n_hub_rows < 0) return fail(err, DL_ERR_INVALID, "dl_mix_round: n_hub_rows < 0");
+    if (!a->x || !a->y || !W.row_ptr || (W.nnz > 0 && (!W.col || !W.w)))
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: null x/y/row_ptr/col/w");
+    if (a->tile_cols < 0 || (a->tile_cols > 0 && (a->tile_cols % 4 || a->tile_cols < 4 ||
+                                                   a->tile_cols > 4 * kMaxChunks ||
+                                                   (a->tile_cols & (a->tile_cols - 1)))))
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: tile_cols must be 0 or a power of two in [4, %d]",
+                    4 * kMaxChunks);
+    const bool tiled = a->tile_cols > 0;
+    if (!tiled && (a->ldx < a->n_params || a->ldy < a->n_params))
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: ldx/ldy smaller than n_params");
+    if (!tiled && a->g && a->ldg < a->n_params)
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: ldg < n_params");
+    // column-tiled: ld* = rows of each operand's tiled blocks (0 = the operand's own rows)
+    if (tiled && (a->ldx < 0 || a->ldy < 0 || a->ldg < 0 || (a->ldx > 0 && a->ldx < NL) ||
+                  (a->ldy > 0 && a->ldy < W.n_rows) || (a->g && a->ldg > 0 && a->ldg < NL) ||
+                  a->ldx > 65535 * 4 || a->ldy > 65535 * 4 || a->ldg > 65535 * 4))
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: tiled ldx/ldg (>= n_local_src) or "
+                                         "ldy (>= n_rows) out of range");
+    if (a->n_halo > 0 && !a->halo)
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: n_halo > 0 needs a halo buffer");
+    if (!tiled && a->n_halo > 0 && a->ldh < a->n_params)
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: n_halo > 0 needs halo with ldh >= n_params");
+    if (!tiled && a->n_halo_blocks != 0)
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: n_halo_blocks is for the column-tiled layout");
+    if (tiled && a->n_halo > 0) {
+        if (a->n_halo_blocks < 0 || a->n_halo_blocks > kMaxHaloBlocks ||
+            (a->n_halo_blocks > 0 && !a->halo_block_rows))
+            return fail(err, DL_ERR_INVALID, "dl_mix_round: n_halo_blocks must be 0..%d with "
+                                             "halo_block_rows", kMaxHaloBlocks);
+        int64_t sum = 0;
+        for (int b = 0; b < a->n_halo_blocks; ++b) {
+            if (a->halo_block_rows[b] <= 0)
+                return fail(err, DL_ERR_INVALID, "dl_mix_round: halo_block_rows[%d] <= 0", b);
+            sum += a->halo_block_rows[b];
+        }
+        if (a->n_halo_blocks > 0 && sum != a->n_halo)
+            return fail(err, DL_ERR_INVALID,
+                        "dl_mix_round: halo_block_rows sum to %lld, n_halo %d", (long long)sum,
+                        a->n_halo);
+        const int64_t ntl = (a->n_params + a->tile_cols - 1) / a->tile_cols;
+        if (ntl * a->n_halo * a->tile_cols * 4 >= ((int64_t)1 << 32))
+            return fail(err, DL_ERR_INVALID, "dl_mix_round: the tiled halo must span < 4 GiB");
+    }
+    // a column-tiled partition round reads mean_prev / colsum_out a float4 per chunk, tiles whole
+    if (tiled && part && a->n_params % a->tile_cols)
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: a column-tiled partition round needs "
+                                         "n_params %% tile_cols == 0");
+    if (W.uniform_row_nnz < 0 ||
+        (W.uniform_row_nnz > 0 && (int64_t)W.uniform_row_nnz * W.n_rows != W.nnz))
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: uniform_row_nnz * n_rows != nnz");
+    if (W.shared_row_weights && W.uniform_row_nnz <= 0)
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: shared_row_weights needs uniform_row_nnz > 0");
+    if (W.min_row_nnz < 0 || (int64_t)W.min_row_nnz * W.n_rows > W.nnz)
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: min_row_nnz * n_rows > nnz");
+    if ((a->mean_prev || a->colsum_out) && !part)
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: mean_prev / colsum_out are for halo rounds "
+                    "(n_halo > 0 or n_local_src != n_rows); local rounds fuse "
+                    "the exact deviation");
+    if (a->mean && part)
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: the column mean of a halo round is global: "
+                    "use colsum_out and an all-reduce");
+    if ((a->dev_sq || a->dev_max || a->mean_prev || a->colsum_out) && part &&
+        !(a->mean_prev && a->colsum_out))
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: a halo round's deviation is the lagged one: mean_prev, "
+                    "colsum_out and dev_sq together, or both without dev_sq (partial rows left "
+                    "in the workspace), or dl_column_sum + dl_deviation after it");
+    if (part && a->mean_prev && !a->dev_sq && a->tile_cols <= 0)
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: partial rows without dev_sq need the "
+                    "column-tiled layout (one launch, plan grid rows)");
+    if (part && a->mean_prev && !a->dev_sq && !a->partial_rows_out)
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_round: a lagged halo round without dev_sq leaves its "
+                    "deviation as partial rows: pass partial_rows_out (ABI 9) to "
+                    "receive their count, or dev_sq for the reduced deviation");
+    // extents: a tiled operand of `rows` used rows inside blocks of `ld` rows spans (tiles - 1)
+    // block strides plus its used rows of the last tile
+    const int64_t Tc = a->tile_cols;
+    const int64_t ntl = tiled ? (a->n_params + Tc - 1) / Tc : 0;
+    auto extent = [&](int64_t ld, int64_t rows) {
+        return tiled ? (size_t)(((ntl - 1) * (ld ? ld : rows) + rows) * Tc * 4)
+                     : ((size_t)(rows - 1) * ld + a->n_params) * 4;
+    };
+    const size_t yb = extent(a->ldy, W.n_rows);
+    if (overlaps(a->x, extent(a->ldx, NL), a->y, yb))
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: y overlaps x");
+    if (a->g && overlaps(a->g, extent(a->ldg, NL), a->y, yb))
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: y overlaps g");
+    if (a->n_halo > 0) {
+        const size_t hb = tiled ? (size_t)(ntl * a->n_halo * Tc * 4) : extent(a->ldh, a->n_halo);
+        if (overlaps(a->halo, hb, a->y, yb))
+            return fail(err, DL_ERR_INVALID, "dl_mix_round: y overlaps halo");
+    }
+    return DL_OK;
+}
+
+TileArgs tile_args(const dl_mix_args &a, const Knobs &k) {
+    TileArgs t{};
+    t.x = a.x;
+    t.ldx = a.ldx;
+    t.halo = a.halo;
+    t.ldh = a.ldh;
+    t.g = a.g;
+    t.ldg = a.ldg;
+    t.y = a.y;
+    t.ldy = a.ldy;
+    t.rowptr = a.W.row_ptr;
+    t.col = a.W.col;
+    t.w = a.W.w;
+    t.n_rows = a.W.n_rows;
+    t.n_loc = local_src(a);
+    t.n_src = t.n_loc + a.n_halo;
+    t.nnz = a.W.nnz;
+    t.regular = a.W.uniform_row_nnz;
+    t.n_w = (a.W.uniform_row_nnz > 0 && a.W.shared_row_weights) ? a.W.uniform_row_nnz : a.W.nnz;
+    t.mean_from_inputs = (a.W.doubly_stochastic && t.n_src == t.n_rows) ? 1 : 0;
+    // X, G and X' are streamed exactly once per round: non-temporal loads and stores keep them
+    // out of L2/MALL (measured +1.5 % on c2).  An X' that fits the 256-MB MALL is stored plainly
+    // instead, so the next kernel's reads of it (the c3 gradient launch reading X' as its
+    // parameters) can hit there: c3 +2 % steps/s (3743 vs 3668) -- but not in a partitioned
+    // round, whose next launch is the next column chunk's pack and mix (other columns): plain
+    // stores there left the following launch 16 % slower (one rank of 8, two chunks of 256 MB:
+    // 421.7 against 383.5-387.5 us a round with them non-temporal, profiles/r13/c4rank_env/).
+    // Knobs::nt_store / nt_load force them.
+    const size_t y_bytes = (size_t)a.W.n_rows * (size_t)a.n_params * 4;
+    t.nt_store = k.nt_store >= 0 ? k.nt_store
+                                 : (y_bytes > kMallBytes || mix_partitioned(a) ? 1 : 0);
+    t.nt_load = k.nt_load;
+    t.n_params = a.n_params;
+    t.lr = a.lr;
+    // float4 access: every operand given 16-byte aligned, and row-major rows too (ld % 4)
+    bool vec = aligned16(a.x) && aligned16(a.y) && aligned16(a.g) && aligned16(a.halo) &&
+               aligned16(a.mean) && aligned16(a.mean_prev) && aligned16(a.colsum_out);
+    if (a.tile_cols <= 0)
+        vec = vec && a.ldx % 4 == 0 && a.ldy % 4 == 0 && (!a.g || a.ldg % 4 == 0) &&
+              (!a.halo || a.ldh % 4 == 0);
+    t.mean_prev = a.mean_prev;
+    t.colsum_out = a.colsum_out;
+    // the float4 kernel addresses rows with 32-bit byte offsets from the tile base
+    const int64_t lim = (int64_t)1 << 32;
+    const int64_t R = t.n_loc > t.n_rows ? t.n_loc : t.n_rows;
+    if (a.tile_cols > 0) {
+        t.tiled = 1;
+        // per-peer halo blocks (check_mix_args: <= kMaxHaloBlocks, rows summing to n_halo, the
+        // whole halo < 4 GiB)
+        const int64_t Tc = a.tile_cols;
+        const int64_t ntl = (a.n_params + Tc - 1) / Tc;
+        const int nb = a.n_halo > 0 ? (a.n_halo_blocks > 0 ? a.n_halo_blocks : 1) : 0;
+        t.n_hblk = nb;
+        int32_t r0 = 0;
+        for (int b = 0; b < nb; ++b) {
+            t.hblk_row0[b] = r0;
+            t.hblk_off[b] = (uint32_t)(ntl * r0 * Tc * 4);
+            r0 += a.n_halo_blocks > 0 ? a.halo_block_rows[b] : a.n_halo;
+        }
+        t.hblk_row0[nb] = r0;
+    } else if (((R - 1) * a.ldx + 128) * 4 >= lim || ((R - 1) * a.ldy + 128) * 4 >= lim ||
+               (a.g && ((R - 1) * a.ldg + 128) * 4 >= lim) ||
+               // a halo row's offset (row and column) is one 32-bit value
+               (a.n_halo > 0 && (int64_t)a.n_halo * a.ldh * 4 >= lim)) {
+        vec = false;
+    }
+    t.vec = vec ? 1 : 0;
+    t.mean = a.mean;
+    return t;
+}
+
+int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_t ws_bytes,
+                Launches *out, char *err) {
+    reset(out);
+    Plan pl;
+    int rc = plan_mix(a, n_cus, k, &pl, err);
+    if (rc) return rc;
+    const int32_t Nr = a.W.n_rows;
+    Launch &l = out->l[0];
+    l.t = tile_args(a, k);
+    TileArgs &t = l.t;
+    l.sgd = a.g != nullptr;
+    l.dev = pl.dev;   // a lagged halo round always writes its deviation partials
+    l.mix = true;
+    // lagged halo rounds: one partial row per local source row
+    const bool lag = tile_lag(t);
+    const int32_t Np = lag ? t.n_loc : Nr;
+    if (pl.dev && !ws_holds(ws, ws_bytes, 0))
+        return fail(err, DL_ERR_WORKSPACE, "dl_mix_round: deviation outputs need a 16-byte "
+                                           "aligned workspace of dl_mix_workspace_bytes()");
+    // the register-CSR kernels (paths 4 / 5) are FAST-only and the gather kernel reads row-major
+    // operands only: unaligned column-tiled operands are refused, unaligned row-major ones of
+    // paths 4 / 5 take the gather path
+    if (t.tiled && !t.vec)
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: tiled operands must be 16-byte aligned");
+    if (pl.pub.path == 2 || (pl.pub.path != 1 && !t.vec)) {
+        l.kind = kLaunchGather;
+        l.columns = k.gather_order_columns;
+        out->n = 1;
+        if (pl.dev) out->after = Nr <= 1 ? kAfterZero : kAfterTwoPass;
+        return DL_OK;
+    }
+    const bool reg_csr = pl.pub.path != 1;
+    const int64_t T = pl.pub.tile_cols;
+    set_tile_strides(t, T);
+    const Split s = split_tiles(t, T, pl.pub.n_tiles, pl.pub.grid);
+    const size_t need = partial_bytes(s.parts(), Np);
+    if (pl.dev && ws_bytes < need)
+        return fail(err, DL_ERR_WORKSPACE, "dl_mix_round: workspace %zu < %zu bytes", ws_bytes,
+                    need);
+    if (reg_csr && s.grid_tail > 0)
+        return fail(err, DL_ERR_INVALID, "dl_mix_round: register-CSR plan with a tail");
+    t.csr_off = pl.csr_off;
+    t.scratch_off = pl.scratch_off;
+    if (pl.grp > 1) {   // tile groups: chunk c of a kernel row -> data tile c / (T / 4)
+        t.grp = pl.grp;
+        t.cd_sh = __builtin_ctz((unsigned)(T / 4));
+    }
+    float *partial = pl.dev ? static_cast<float *>(ws) : nullptr;
+    if (pl.dev) t.dev_max_zero = reinterpret_cast<unsigned int *>(a.dev_max);
+    int lds = pl.pub.lds_bytes;
+    // Knobs::lds_min, a measurement knob: LDS per workgroup bounds workgroups per CU
+    if (k.lds_min > lds) lds = k.lds_min < kLdsBytes ? k.lds_min : kLdsBytes;
+    if (pl.pub.path == 5 && pl.head < 5 && a.n_hub_rows > 0) {
+        // hub rows' register heads behind the LDS tail: as many as fit, <= 256
+        const int hb = pl.head * 8;
+        const int room = (kLdsBytes - lds) / hb;
+        int nh = a.n_hub_rows < 256 ? a.n_hub_rows : 256;
+        if (nh > Nr) nh = Nr;
+        if (nh > room) nh = room;
+        if (nh > 0) {
+            t.n_hub = nh;
+            t.hub_off = (uint32_t)((lds + 15) & ~15);
+            lds = (int)t.hub_off + nh * hb;
+            if (lds > kLdsBytes) {   // (alignment) fall back to no hub lanes
+                t.n_hub = 0;
+                lds = pl.pub.lds_bytes;
+            }
+        }
+    }
+    l.kind = reg_csr ? kLaunchTileReg : kLaunchTile;
+    l.chunks = pl.chunks;
+    l.head = pl.head;
+    l.tail_fmt = pl.tail_fmt;
+    l.lds = lds;
+    // row-major operands: each workgroup walks one contiguous run of tiles instead of every
+    // grid-th tile, so its row segments follow each other in every row (c3's 256 x 164,608
+    // round: 103.8 against 105.3-107.3 us between events, profiles/r13/c3_env/); the
+    // column-tiled layout keeps the grid stride (+0.4 % with runs on c2, within noise).
+    // Knobs::tile_run forces it off / on.
+    push_split(out, s, T, partial, Np, k.tile_run >= 0 ? k.tile_run == 1 : !t.tiled);
+    if (!pl.dev) return DL_OK;
+    // a lagged round without dev_sq leaves its partial rows to the caller (column chunks reduced
+    // once, dl_row_sums) and says how many; its dev_max, if any, the kernel zeroed
+    if (Nr <= 1 && !lag) {
+        out->after = kAfterZero;
+    } else if (lag && !a.dev_sq) {
+        out->after = kAfterPartialRows;
+        out->parts = s.parts();
+    } else {
+        after_reduce(out, partial, s.parts(), Np, true);
+    }
+    return DL_OK;
+}
+
+int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
+                 size_t ws_bytes, Launches *out, char *err) {
+    reset(out);
+    if (rounds < 1) return fail(err, DL_ERR_INVALID, "dl_mix_rounds: rounds must be >= 1");
+    Plan pl;
+    int rc = plan_rounds(a, n_cus, k, &pl, err);
+    if (rc) return rc;
+    const int32_t Nr = a.W.n_rows;
+    Launch &l = out->l[0];
+    l.t = tile_args(a, k);
+    TileArgs &t = l.t;
+    if (!t.vec)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_mix_rounds: operands must be 16-byte aligned "
+                                             "float4 rows");
+    set_tile_strides(t, pl.pub.tile_cols);
+    t.n_tiles = pl.pub.n_tiles;
+    t.col_base = 0;
+    t.csr_off = pl.csr_off;
+    t.scratch_off = pl.scratch_off;
+    if (pl.dev) {
+        const size_t need = partial_bytes(pl.pub.grid, Nr);
+        if (!ws_holds(ws, ws_bytes, need))
+            return fail(err, DL_ERR_WORKSPACE, "dl_mix_rounds: deviation outputs need a "
+                                               "16-byte aligned workspace of %zu bytes", need);
+        t.dev_partial = static_cast<float *>(ws);
+        t.dev_max_zero = reinterpret_cast<unsigned int *>(a.dev_max);
+    }
+    l.kind = kLaunchMulti;
+    l.chunks = pl.chunks;
+    l.rounds = rounds;
+    l.sgd = a.g != nullptr;
+    l.dev = pl.dev;
+    l.grid = pl.pub.grid;
+    l.lds = pl.pub.lds_bytes;
+    out->n = 1;
+    if (pl.dev) {
+        if (Nr <= 1) out->after = kAfterZero;
+        else after_reduce(out, t.dev_partial, pl.pub.grid, Nr, true);
+    }
+    return DL_OK;
+}
+
+int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
+                size_t ws_bytes, Launches *out, char *err) {
+    reset(out);
+    TracePlan tp;
+    int rc = plan_trace(a, n_cus, k, &tp, err);
+    if (rc) return rc;
+    if (rounds < 1 || rounds > tp.max_rounds)
+        return fail(err, DL_ERR_INVALID, "dl_mix_rounds_trace: rounds must be in [1, %d] (one "
+                                         "traced pass), got %d", tp.max_rounds, rounds);
+    Launch &l = out->l[0];
+    l.t = tile_args(a, k);
+    TileArgs &t = l.t;
+    if (!t.vec)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_mix_rounds_trace: operands must be 16-byte "
+                                             "aligned float4 rows");
+    if (tp.irr && t.tiled && a.tile_cols % 4)
+        return fail(err, DL_ERR_INVALID,
+                    "dl_mix_rounds_trace: tile_cols must be a multiple of 4");
+    // a step walks float4 chunks: of an operand tile when column-tiled, else of the row itself
+    t.lchunks = t.tiled ? a.tile_cols / 4 : 1;
+    set_tile_strides(t, t.tiled ? a.tile_cols : 4);
+    t.n_tiles = (int32_t)tp.n_steps;
+    t.csr_off = tp.csr_off;
+    t.scratch_off = tp.scratch_off;
+    const size_t need = partial_bytes((int64_t)tp.grid * rounds, a.W.n_rows);
+    if (!ws_holds(ws, ws_bytes, need))
+        return fail(err, DL_ERR_WORKSPACE, "dl_mix_rounds_trace: needs a 16-byte aligned "
+                                           "workspace of %zu bytes "
+                                           "(dl_mix_trace_workspace_bytes)", need);
+    t.dev_partial = static_cast<float *>(ws);
+    l.kind = tp.irr ? kLaunchTraceIrr : kLaunchTrace;
+    l.chunks = tp.chunks;
+    l.head = tp.head;
+    l.gm = tp.gm != 0;
+    l.narrow = tp.narrow != 0;
+    l.planes = k.trace_planes;
+    l.rounds = rounds;
+    l.grid = tp.grid;
+    l.lds = (int32_t)tp.lds;
+    out->n = 1;
+    return DL_OK;
+}
+
+int shape_deviation(const float *x, int64_t ldx, int32_t tile_cols, int32_t n_rows,
+                    int64_t n_params, float *mean_out, int n_cus, void *ws, size_t ws_bytes,
+                    Launches *out, char *err) {
+    reset(out);
+    int c = tile_cols > 0 ? tile_cols / 4 : next_pow2_chunks(n_params);
+    for (; c >= 1; c >>= 1) {
+        if ((int64_t)n_rows * c <= (int64_t)kRowsPerThread * kTileThreads) break;
+        if (tile_cols > 0) return DL_ERR_UNSUPPORTED;
+    }
+    if (c < 1) return DL_ERR_UNSUPPORTED;
+    const int64_t T = 4 * c;
+    bool vec = aligned16(x) && (!mean_out || aligned16(mean_out));
+    if (tile_cols == 0)
+        vec = vec && ldx % 4 == 0 && ((int64_t)(n_rows - 1) * ldx + 128) * 4 < ((int64_t)1 << 32);
+    else if (!vec)
+        return fail(err, DL_ERR_INVALID, "dl_deviation_tiled: x must be 16-byte aligned");
+    Launch &l = out->l[0];
+    TileArgs &t = l.t;
+    t.x = x;
+    t.ldx = ldx;
+    t.n_rows = n_rows;
+    t.n_src = n_rows;
+    t.n_loc = n_rows;
+    t.n_params = n_params;
+    t.vec = vec ? 1 : 0;
+    t.mean = mean_out;
+    t.tiled = tile_cols > 0 ? 1 : 0;
+    tile_stride(t.tiled, ldx, n_rows, T, &t.xts, &t.xrs);
+    const Split s = split_tiles(t, T, (n_params + T - 1) / T, (int64_t)n_cus * 2);
+    if (ws_bytes < partial_bytes(s.parts(), n_rows))
+        return fail(err, DL_ERR_WORKSPACE, "dl_deviation: workspace too small");
+    l.kind = kLaunchTile;
+    l.chunks = c;
+    l.dev = true;
+    l.lds = (kTileThreads / 64) * c * 16;
+    float *partial = static_cast<float *>(ws);
+    push_split(out, s, T, partial, n_rows, false);
+    after_reduce(out, partial, s.parts(), n_rows, false);
+    return DL_OK;
+}
+
+}  // namespace dl

@@ -1,0 +1,158 @@
+// Launch shaping of the gossip rounds: host-only C++17, no HIP, like the planner beside it.  Pure
+// functions of (args, compute units, knobs, workspace pointer and size) that validate a call and
+// describe what it launches -- every kernel's TileArgs, grid, LDS bytes and selectors, and the
+// step after the launches; the C ABI (capi.hip) turns the description into launch_* calls.
+#pragma once
+#include "plan.h"
+
+namespace dl {
+
+struct TileArgs {
+    const float *x;
+    int64_t ldx;
+    const float *halo;
+    int64_t ldh;
+    const float *g;
+    int64_t ldg;
+    float *y;
+    int64_t ldy;
+    const int32_t *rowptr;
+    const int32_t *col;
+    const float *w;
+    int32_t n_rows;   // output rows (local agents)
+    int32_t n_src;    // rows staged in LDS = n_loc + n_halo
+    int32_t n_loc;    // source rows read from x (and stepped with g); n_rows unless the round
+                      // mixes one row set of an agent partition from a wider local window
+    int32_t nnz;
+    int32_t regular;  // >0: every row has exactly `regular` entries (row_ptr not staged)
+    int32_t n_w;      // weights staged in LDS: nnz, or `regular` when every row shares row 0's
+    int32_t mean_from_inputs;  // 1: W doubly stochastic -> tile mean taken from the staged t
+    int32_t nt_store;          // 1: non-temporal stores of y (FAST path)
+    int32_t nt_load;           // non-temporal loads (FAST path): bit 0 x / halo, bit 1 g
+    int64_t n_params;
+    int32_t n_tiles;
+    int64_t col_base; // first column of tile 0
+    float lr;
+    int32_t vec;      // 1: x/g/y/halo 16-byte aligned and ld % 4 == 0
+    uint32_t csr_off; // byte offset of the staged CSR in LDS
+    uint32_t scratch_off; // byte offset of the 16 x C float4 mean scratch in LDS
+    // FAST-path strides in bytes: tile stride (next tile's row 0) and row stride.
+    //   row-major:      xts = T*4,          xrs = ldx*4   (tile base also offset by col_base)
+    //   column-tiled:   xts = n_rows*T*4,   xrs = T*4     (block [n_rows][T] per tile)
+    int32_t tiled;
+    int64_t xts, gts, yts;
+    uint32_t xrs, grs, yrs;
+    uint32_t hrs;     // halo row stride in bytes (ldh*4)
+    int32_t lchunks;     // mix_trace_kernel: float4 chunks per operand tile (1 = row-major)
+    float *dev_partial;  // [gridDim.x][n_rows] per-workgroup partial ||y_a - mean||^2
+                         // (lagged halo deviation: [gridDim.x][n_loc], one per source row)
+    float *mean;         // [n_params] nullable
+    unsigned int *dev_max_zero;  // nullable: workgroup 0 zeroes it (dev_reduce's atomicMax target,
+                                 // so that launch needs no memset of its own)
+    const float *mean_prev;      // halo rounds: global column mean of x (lagged deviation)
+    float *colsum_out;           // halo rounds: this rank's column sums of y
+    // column-tiled halo (tiled != 0, n_src > n_loc): n_hblk per-peer blocks back to back; block
+    // b holds halo rows [hblk_row0[b], hblk_row0[b + 1]) as [n_tiles][rows_b][T], starting
+    // hblk_off[b] bytes into `halo`
+    int32_t n_hblk;
+    int32_t hblk_row0[17];
+    uint32_t hblk_off[16];
+    // path 5: rows [0, n_hub) folded by four column lanes each; their register heads as
+    // {weight, row} pairs at LDS byte offset hub_off
+    int32_t n_hub;
+    uint32_t hub_off;
+    // column-tiled partition rounds (FAST): one kernel tile = `grp` consecutive data tiles of T
+    // columns (chunk c of a kernel row is chunk c & (2^cd_sh - 1) of data tile c >> cd_sh), so a
+    // short launch moves grp times the bytes per pass; grp = 1 (the default) is the plain tile
+    int32_t grp;
+    int32_t cd_sh;
+    int32_t tile_run;          // 0: workgroup b walks tiles b, b + grid, ...; > 0: the run
+                               // [b * tile_run, (b + 1) * tile_run) (Knobs::tile_run)
+};
+constexpr int kMaxHaloBlocks = 16;
+
+// a round of an agent partition: halo source rows, or output rows that are not the source rows
+inline bool mix_partitioned(const dl_mix_args &a) {
+    return a.n_halo > 0 || local_src(a) != a.W.n_rows;
+}
+inline bool tile_partitioned(const TileArgs &a) {
+    return a.n_src != a.n_rows || a.n_loc != a.n_rows;
+}
+// ... with the lagged deviation (the halo instantiations' LAG)
+inline bool tile_lag(const TileArgs &a) {
+    return tile_partitioned(a) && (a.mean_prev != nullptr || a.colsum_out != nullptr);
+}
+
+constexpr size_t kWsAlign = 256;
+constexpr size_t align_up(size_t v) { return (v + kWsAlign - 1) & ~(kWsAlign - 1); }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// do the an bytes at a and the bn bytes at b share a byte
+inline bool overlaps(const void *a, size_t an, const void *b, size_t bn) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bn && y < x + an;
+}
+// workspace bytes of `parts` partial rows of `rows` floats, and whether ws holds `need` of them
+constexpr size_t partial_bytes(int64_t parts, int64_t rows) {
+    return align_up((size_t)parts * (size_t)rows * 4);
+}
+inline bool ws_holds(const void *ws, size_t ws_bytes, size_t need) {
+    return ws && aligned16(ws) && ws_bytes >= need;
+}
+
+// One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
+// launch_* functions of dl_internal.h take them.
+enum LaunchKind : int32_t {
+    kLaunchTile,      // launch_mix_tile(t, chunks, sgd, dev, mix, grid, lds, fast)
+    kLaunchTileReg,   // launch_mix_tile_reg(t, chunks, head, tail_fmt, sgd, dev, grid, lds)
+    kLaunchGather,    // launch_mix_gather(t, sgd, columns)
+    kLaunchMulti,     // launch_mix_multi(t, chunks, rounds, sgd, dev, grid, lds)
+    kLaunchTrace,     // launch_mix_trace(t, chunks, planes, rounds, grid, lds, trace): + its reduce
+    kLaunchTraceIrr,  // launch_mix_trace_irr(t, head, gm, narrow, rounds, grid, lds, trace): same
+};
+struct Launch {
+    int32_t kind;
+    int32_t grid, lds;
+    int32_t chunks, head, tail_fmt, rounds;
+    bool sgd, dev, mix, fast;
+    bool columns;              // gather: Knobs::gather_order_columns
+    bool planes, gm, narrow;   // traced passes
+    TileArgs t;
+};
+// What follows the launches on the stream.
+enum After : int32_t {
+    kAfterNothing,
+    kAfterZero,         // zero dev_sq / dev_max (one agent: no deviation)
+    kAfterReduce,       // launch_dev_reduce(partial, parts, rows, dev_sq, dev_max, max_zeroed)
+    kAfterPartialRows,  // leave the partial rows in the workspace, *partial_rows_out = parts
+    kAfterTwoPass,      // the two-pass deviation of y (the gather path)
+};
+struct Launches {
+    int32_t n;
+    Launch l[2];
+    int32_t after;
+    const float *partial;   // kAfterReduce
+    int32_t parts, rows;    // kAfterReduce, kAfterPartialRows (parts)
+    bool max_zeroed;
+};
+
+// Argument check of every round entry point; the texts say dl_mix_round for all of them.
+int check_mix_args(const dl_mix_args *a, char *err);
+// The kernels' view of a round's operands: sizes, float4 eligibility, cache policy, halo blocks.
+TileArgs tile_args(const dl_mix_args &a, const Knobs &k);
+
+// The entry points, after check_mix_args: plan (plan.h) and shape.  Each returns a dl_status
+// and, on failure, the dl_last_error() text in err[kErrLen].
+int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_t ws_bytes,
+                Launches *out, char *err);
+int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
+                 size_t ws_bytes, Launches *out, char *err);
+int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
+                size_t ws_bytes, Launches *out, char *err);
+// One-pass deviation of x on the tile kernel (MIX = false): every agent of a column tile in one
+// workgroup, column mean in LDS scratch.  tile_cols > 0: x in the column-tiled layout (ldx 0).
+// DL_ERR_UNSUPPORTED without a text: the agents do not fit one tile.
+int shape_deviation(const float *x, int64_t ldx, int32_t tile_cols, int32_t n_rows,
+                    int64_t n_params, float *mean_out, int n_cus, void *ws, size_t ws_bytes,
+                    Launches *out, char *err);
+
+}  // namespace dl

@@ -324,12 +324,7 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
 
 template <int C, int KV, bool SGD, bool DEV, int RE, int MODE>
 hipError_t launch_mode(const TileArgs &a, int rounds, int grid, int lds, hipStream_t s) {
-    const void *k = reinterpret_cast<const void *>(mix_multi_kernel<C, KV, SGD, DEV, RE, MODE>);
-    hipError_t e = allow_full_lds(k);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((mix_multi_kernel<C, KV, SGD, DEV, RE, MODE>), dim3(grid),
-                       dim3(kTileThreads), lds, s, a, rounds);
-    return hipGetLastError();
+    return launch_lds(mix_multi_kernel<C, KV, SGD, DEV, RE, MODE>, grid, lds, s, a, rounds);
 }
 
 template <int C, int KV, bool SGD, bool DEV, int RE>

@@ -1008,11 +1008,8 @@ __global__ void __launch_bounds__(1024) stream_triad_tile_kernel(const float4 *_
 template <int C, int KV, bool SGD, bool DEV, bool MIX, int HALO, bool FAST, int RD = 0,
           bool LAG = false, int RAG = 0>
 hipError_t launch_one(const TileArgs &a, int grid, int lds, hipStream_t s) {
-    auto k = mix_tile_kernel<C, KV, SGD, DEV, MIX, HALO, FAST, RD, LAG, RAG>;
-    hipError_t e = allow_full_lds(reinterpret_cast<const void *>(k));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kTileThreads), lds, s, a);
-    return hipGetLastError();
+    return launch_lds(mix_tile_kernel<C, KV, SGD, DEV, MIX, HALO, FAST, RD, LAG, RAG>, grid, lds, s,
+                      a);
 }
 
 template <int C, int KV, bool FAST, int H>
@@ -1138,12 +1135,11 @@ hipError_t allow_full_lds(const void *k) {
     return e;
 }
 
-hipError_t launch_mix_gather(const TileArgs &a, bool sgd, hipStream_t s) {
+hipError_t launch_mix_gather(const TileArgs &a, bool sgd, bool columns, hipStream_t s) {
     const unsigned chunks = (unsigned)((a.n_params + 255) / 256);
     const unsigned groups = (unsigned)((a.n_rows + 3) / 4);
-    // DLAMD_GATHER_ORDER=columns keeps the column-fastest order (measurement knob)
-    const char *o = getenv("DLAMD_GATHER_ORDER");
-    const bool agent_fast = !(o && o[0] == 'c') && chunks <= 65535;
+    // columns keeps the column-fastest order (a measurement knob)
+    const bool agent_fast = !columns && chunks <= 65535;
     if (agent_fast) {
         dim3 grid(groups, chunks);
         if (sgd)

@@ -915,28 +915,14 @@ __global__ void __launch_bounds__(1024) trace_reduce_kernel(const float *__restr
 
 template <int RE, int C>
 hipError_t launch_rc(const TileArgs &a, int rounds, int grid, int lds, hipStream_t s) {
-    const void *k = reinterpret_cast<const void *>(mix_trace_kernel<RE, C>);
-    hipError_t e = allow_full_lds(k);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((mix_trace_kernel<RE, C>), dim3(grid), dim3(kTileThreads), lds, s, a,
-                       rounds);
-    return hipGetLastError();
+    return launch_lds(mix_trace_kernel<RE, C>, grid, lds, s, a, rounds);
 }
 
 template <int KV, int KR>
 hipError_t launch_rows(const TileArgs &a, int rounds, int grid, int lds, hipStream_t s) {
     const bool full = a.n_rows == KV * (kTileThreads / 4);
-    const void *k = full ? reinterpret_cast<const void *>(mix_trace_rows_kernel<KV, KR, true>)
-                         : reinterpret_cast<const void *>(mix_trace_rows_kernel<KV, KR, false>);
-    hipError_t e = allow_full_lds(k);
-    if (e != hipSuccess) return e;
-    if (full)
-        hipLaunchKernelGGL((mix_trace_rows_kernel<KV, KR, true>), dim3(grid), dim3(kTileThreads),
-                           lds, s, a, rounds);
-    else
-        hipLaunchKernelGGL((mix_trace_rows_kernel<KV, KR, false>), dim3(grid), dim3(kTileThreads),
-                           lds, s, a, rounds);
-    return hipGetLastError();
+    return launch_lds(full ? mix_trace_rows_kernel<KV, KR, true>
+                           : mix_trace_rows_kernel<KV, KR, false>, grid, lds, s, a, rounds);
 }
 
 template <int RE>
@@ -954,29 +940,17 @@ template <int KV, int RE>
 hipError_t launch_wide(const TileArgs &a, int rounds, int grid, int lds, hipStream_t s) {
     constexpr int KR = KV > 2 ? kWideTraceRounds4 : kWideTraceRounds2;
     const bool full = a.n_rows == KV * kTileThreads;
-    const void *k = full ? reinterpret_cast<const void *>(mix_trace_wide_kernel<KV, KR, RE, true>)
-                         : reinterpret_cast<const void *>(mix_trace_wide_kernel<KV, KR, RE, false>);
-    hipError_t e = allow_full_lds(k);
-    if (e != hipSuccess) return e;
-    if (full)
-        hipLaunchKernelGGL((mix_trace_wide_kernel<KV, KR, RE, true>), dim3(grid),
-                           dim3(kTileThreads), lds, s, a, rounds);
-    else
-        hipLaunchKernelGGL((mix_trace_wide_kernel<KV, KR, RE, false>), dim3(grid),
-                           dim3(kTileThreads), lds, s, a, rounds);
-    return hipGetLastError();
+    return launch_lds(full ? mix_trace_wide_kernel<KV, KR, RE, true>
+                           : mix_trace_wide_kernel<KV, KR, RE, false>, grid, lds, s, a, rounds);
 }
 
 template <int KV, int RD, bool GM>
 hipError_t launch_irr3(const TileArgs &a, bool narrow, int rounds, int grid, int lds,
                        hipStream_t s) {
     constexpr int KR = irr_trace_rounds(KV);
-    auto k = narrow ? mix_trace_irr_kernel<KV, KR, RD, GM, true>
-                    : mix_trace_irr_kernel<KV, KR, RD, GM, false>;
-    hipError_t e = allow_full_lds(reinterpret_cast<const void *>(k));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kTileThreads), lds, s, a, rounds);
-    return hipGetLastError();
+    return launch_lds(narrow ? mix_trace_irr_kernel<KV, KR, RD, GM, true>
+                             : mix_trace_irr_kernel<KV, KR, RD, GM, false>,
+                      grid, lds, s, a, rounds);
 }
 
 template <int KV, bool GM>
@@ -1001,6 +975,14 @@ hipError_t launch_irr1(const TileArgs &a, int head, bool narrow, int rounds, int
     return launch_irr2<4, GM>(a, head, narrow, rounds, grid, lds, s);
 }
 
+// the traced kernel's [grid][rounds][n_rows] partials -> trace_out[rounds]
+hipError_t launch_trace_reduce(const TileArgs &a, int rounds, int grid, float *trace_out,
+                               hipStream_t s) {
+    hipLaunchKernelGGL(trace_reduce_kernel, dim3(rounds), dim3(1024), 0, s, a.dev_partial, grid,
+                       rounds, a.n_rows, trace_out);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_mix_trace_irr(const TileArgs &a, int head, bool general_mean, bool narrow,
@@ -1010,10 +992,7 @@ hipError_t launch_mix_trace_irr(const TileArgs &a, int head, bool general_mean, 
         return hipErrorInvalidValue;
     hipError_t e = general_mean ? launch_irr1<true>(a, head, narrow, rounds, grid, lds, s)
                                 : launch_irr1<false>(a, head, narrow, rounds, grid, lds, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(trace_reduce_kernel, dim3(rounds), dim3(1024), 0, s, a.dev_partial, grid,
-                       rounds, a.n_rows, trace_out);
-    return hipGetLastError();
+    return e != hipSuccess ? e : launch_trace_reduce(a, rounds, grid, trace_out, s);
 }
 
 hipError_t launch_mix_trace(const TileArgs &a, int chunks, bool planes, int rounds, int grid,
@@ -1043,10 +1022,7 @@ hipError_t launch_mix_trace(const TileArgs &a, int chunks, bool planes, int roun
         e = in_regs ? launch_re<5>(a, chunks, rounds, grid, lds, s)
                     : launch_re<0>(a, chunks, rounds, grid, lds, s);
     }
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(trace_reduce_kernel, dim3(rounds), dim3(1024), 0, s, a.dev_partial, grid,
-                       rounds, a.n_rows, trace_out);
-    return hipGetLastError();
+    return e != hipSuccess ? e : launch_trace_reduce(a, rounds, grid, trace_out, s);
 }
 
 }  // namespace dl

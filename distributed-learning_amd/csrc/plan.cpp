@@ -26,7 +26,21 @@ Knobs read_knobs() {
     if (const char *v = getenv("DLAMD_MAX_TILE_CHUNKS")) k.max_tile_chunks = atoi(v);
     if (const char *v = getenv("DLAMD_TILE_GROUP")) k.tile_group = atoi(v);
     k.trace_planes = getenv("DLAMD_TRACE_PLANES") != nullptr;
+    if (const char *v = getenv("DLAMD_NT_STORE")) k.nt_store = v[0] == '0' ? 0 : 1;
+    if (const char *v = getenv("DLAMD_NT_LOAD"))
+        k.nt_load = v[0] == '0' ? 0 : v[0] == 'x' ? 1 : v[0] == 'g' ? 2 : 3;
+    if (const char *v = getenv("DLAMD_LDS_MIN")) k.lds_min = atoi(v);
+    if (const char *v = getenv("DLAMD_TILE_RUN")) k.tile_run = v[0] == '1' ? 1 : 0;
+    k.gather_order_columns = is("DLAMD_GATHER_ORDER", 'c');
     return k;
+}
+
+int fail(char *err, int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(err, kErrLen, fmt, ap);
+    va_end(ap);
+    return code;
 }
 
 int max_parts(int n_cus, const Knobs &k) {
@@ -42,14 +56,6 @@ int next_pow2_chunks(int64_t n_params) {
 }
 
 namespace {
-
-int fail(char *err, int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err, kErrLen, fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 uint32_t align256(size_t v) { return (uint32_t)((v + 255) & ~(size_t)255); }
 
@@ -357,12 +363,14 @@ int plan_rounds(const dl_mix_args &a, int n_cus, const Knobs &k, Plan *pl, char 
     const bool want_dev = a.dev_sq || a.dev_max || a.mean;
     pl->dev = want_dev;
     if (a.n_halo > 0 || local_src(a) != R)
-        return fail(err, DL_ERR_UNSUPPORTED, "dl_mix_rounds: halo rows need one exchange per round");
+        return fail(err, DL_ERR_UNSUPPORTED,
+                    "dl_mix_rounds: halo rows need one exchange per round");
     if (want_dev && !a.W.doubly_stochastic)
         return fail(err, DL_ERR_UNSUPPORTED, "dl_mix_rounds: the fused final deviation needs a "
                                              "doubly stochastic W");
     const CsrShape S = csr_shape(a.W);
-    if (S.lds == 0 || R > 65535) return fail(err, DL_ERR_UNSUPPORTED, "dl_mix_rounds: CSR too large");
+    if (S.lds == 0 || R > 65535)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_mix_rounds: CSR too large");
     // degree-4 regular graphs with shared weights keep the CSR in registers (mix_multi.hip
     // launch_kv: uniform_row_nnz 5, 5 weights, <= 4 rows per thread): no LDS for it
     auto layout = [&](int c) {

@@ -15,8 +15,9 @@ constexpr int kLdsBytes = 163840;       // 160 KiB LDS per CU on gfx950
 constexpr int kMaxChunks = 32;          // T <= 128 columns per tile
 constexpr int kErrLen = 512;            // bytes of the planners' error text buffer
 
-// Every environment knob the planner reads.  read_knobs() fills it once per ABI call (not
-// cached: tests and scripts set the variables after the library is loaded).
+// Every environment knob the planner and the launch shaping (launch.h) read.  read_knobs() fills
+// it once per ABI call (not cached: tests and scripts set the variables after the library is
+// loaded).
 struct Knobs {
     int grid_mult = 2;            // DLAMD_GRID_MULT, clamped to 1..8
     bool grid_mult_set = false;   // ... was given: it then applies to short launches too
@@ -27,8 +28,15 @@ struct Knobs {
     int max_tile_chunks = 0;      // DLAMD_MAX_TILE_CHUNKS=c: row-major tiles of <= 4c columns
     int tile_group = 8;           // DLAMD_TILE_GROUP=g: halo tile groups of <= g tiles (1: off)
     bool trace_planes = false;    // DLAMD_TRACE_PLANES set: the chunk-major traced kernel
+    int nt_store = -1;            // DLAMD_NT_STORE=0 / other: plain / non-temporal stores of y
+    int nt_load = 3;              // DLAMD_NT_LOAD=0 / x / g / other: nt_load 0 / 1 / 2 / 3
+    int lds_min = 0;              // DLAMD_LDS_MIN=b: at least b bytes of LDS per tile workgroup
+    int tile_run = -1;            // DLAMD_TILE_RUN=1 / other: contiguous tile runs on / off
+    bool gather_order_columns = false;   // DLAMD_GATHER_ORDER=c...: the column-fastest gather grid
 };
 Knobs read_knobs();
+// Writes the dl_last_error() text of a refusal into err[kErrLen] and returns code.
+int fail(char *err, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 
 struct Plan {
     dl_mix_plan pub;
