@@ -93,6 +93,11 @@ class DlSgdArgs(ctypes.Structure):
                 ("nesterov", _i32), ("first", _i32)]
 
 
+class DlSgdRoundArgs(ctypes.Structure):
+    _fields_ = [("mix", DlMixArgs), ("buf", _vp), ("ldb", _i64), ("momentum", _f32),
+                ("dampening", _f32), ("weight_decay", _f32), ("nesterov", _i32), ("first", _i32)]
+
+
 class DlMlpArgs(ctypes.Structure):
     _fields_ = [("n_agents", _i32), ("batch", _i32), ("input_dim", _i32), ("hidden_dim", _i32),
                 ("output_dim", _i32), ("X", _vp), ("ldx", _i64), ("data", _vp), ("s_data", _i64),
@@ -139,6 +144,8 @@ SIGNATURES = {
                                         _i32, _vp]),
     "dl_stream_copy": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "dl_sgd_step": (_i32, [ctypes.POINTER(DlSgdArgs), _vp]),
+    "dl_sgd_round_plan": (_i32, [ctypes.POINTER(DlSgdRoundArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_sgd_round": (_i32, [ctypes.POINTER(DlSgdRoundArgs), _vp, _sz, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),
     "dl_bgemm": (_i32, [ctypes.POINTER(DlBgemmArgs), _vp]),

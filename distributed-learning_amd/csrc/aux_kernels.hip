@@ -5,6 +5,7 @@
 //   boundary-row local step pack  (multi-GPU halo send buffers)
 //   Perron / asyncio Jacobi round (consensus_asyncio.py:231-310), fp32 and fp64
 #include "dl_internal.h"
+#include "sgd_elem.h"
 
 #include <cstdlib>
 
@@ -173,21 +174,8 @@ __global__ void __launch_bounds__(256) step_rows_tiled_kernel(
 //   d = nesterov ? fma(mu, buf, d) : buf                grad.add(buf, alpha=momentum)
 //   out = fma(-lr, d, x)                                param.add_(grad, alpha=-lr)
 // out may alias x (in-place step) or be the round's input buffer (step fused into the ping-pong).
+// The element arithmetic is sgd_elem (sgd_elem.h).
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-struct SgdParams {
-    float lr, mu, damp, wd;
-    int first, nesterov;
-};
-
-__device__ __forceinline__ float sgd_elem(float x, float g, float &b, const SgdParams &p) {
-    float d = p.wd != 0.f ? __builtin_fmaf(p.wd, x, g) : g;
-    if (p.mu != 0.f) {
-        b = p.first ? d : __builtin_fmaf(1.f - p.damp, d, p.mu * b);
-        d = p.nesterov ? __builtin_fmaf(p.mu, b, d) : b;
-    }
-    return __builtin_fmaf(-p.lr, d, x);
-}
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) sgd_step_kernel(const float *x, int64_t ldx,

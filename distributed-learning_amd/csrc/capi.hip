@@ -663,6 +663,113 @@ int dl_sgd_step(const dl_sgd_args *a, dl_stream_t stream) {
     return e == hipSuccess ? DL_OK : hip_fail(e, "sgd_step launch");
 }
 
+namespace {
+// dl_sgd_round / dl_sgd_round_plan: everything that needs no device, in the header's order
+int check_sgd_round(const dl_sgd_round_args *a) {
+    if (!a) return fail(DL_ERR_INVALID, "dl_sgd_round: args is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y || !m.g) return fail(DL_ERR_INVALID, "dl_sgd_round: null x/y/g");
+    if (m.halo || m.n_halo != 0 || m.mean_prev || m.colsum_out || m.n_local_src != 0 ||
+        m.n_halo_blocks != 0 || m.partial_rows_out)
+        return fail(DL_ERR_UNSUPPORTED, "dl_sgd_round: no halo rows, partition row sets or lagged "
+                                        "deviation (halo, n_halo, mean_prev, colsum_out, "
+                                        "n_local_src, n_halo_blocks, partial_rows_out must be "
+                                        "NULL / 0)");
+    char err[dl::kErrLen];
+    int rc = dl::check_mix_args(&m, err, true);
+    if (rc) return status(rc, err);
+    const bool tiled = m.tile_cols > 0;
+    const int64_t n = m.W.n_rows;
+    if (a->momentum != 0.f &&
+        (!a->buf || (tiled ? a->ldb < 0 || (a->ldb > 0 && a->ldb < n) || a->ldb > 65535 * 4
+                           : a->ldb < m.n_params)))
+        return fail(DL_ERR_INVALID, "dl_sgd_round: momentum needs a buffer laid out as x "
+                                    "(row-major ldb >= n_params; column-tiled ldb 0 or >= n_rows)");
+    if (a->nesterov && (a->momentum <= 0.f || a->dampening != 0.f))
+        return fail(DL_ERR_INVALID, "dl_sgd_round: Nesterov momentum requires a momentum and zero "
+                                    "dampening");
+    if (a->momentum != 0.f) {
+        const int64_t Tc = m.tile_cols;
+        const int64_t ntl = tiled ? (m.n_params + Tc - 1) / Tc : 0;
+        auto extent = [&](int64_t ld) {
+            return tiled ? (size_t)(((ntl - 1) * (ld ? ld : n) + n) * Tc * 4)
+                         : ((size_t)(n - 1) * ld + m.n_params) * 4;
+        };
+        const size_t bb = extent(a->ldb);
+        if (overlaps(a->buf, bb, m.x, extent(m.ldx)) || overlaps(a->buf, bb, m.y, extent(m.ldy)) ||
+            overlaps(a->buf, bb, m.g, extent(m.ldg)))
+            return fail(DL_ERR_INVALID, "dl_sgd_round: buf overlaps x, y or g");
+    }
+    return DL_OK;
+}
+
+// do the float4 kernels reach the momentum buffers: 16-byte aligned, and row-major rows too,
+// within the 32-bit offsets of a tile base (as launch.cpp tile_args asks of x, g and y)
+bool sgd_buf_vec(const dl_sgd_round_args *a) {
+    if (a->momentum == 0.f) return true;
+    if (!aligned16(a->buf)) return false;
+    if (a->mix.tile_cols > 0) return true;
+    return a->ldb % 4 == 0 &&
+           ((int64_t)(a->mix.W.n_rows - 1) * a->ldb + 128) * 4 < ((int64_t)1 << 32);
+}
+}  // namespace
+
+int dl_sgd_round_plan(const dl_sgd_round_args *args, dl_mix_plan *plan) {
+    g_err.clear();
+    int rc = check_sgd_round(args);
+    if (rc) return rc;
+    if (!plan) return fail(DL_ERR_INVALID, "dl_sgd_round_plan: plan is NULL");
+    Plan pl;
+    rc = plan_mix(&args->mix, &pl);
+    if (rc) return rc;
+    if (pl.pub.path != 1)
+        return fail(DL_ERR_UNSUPPORTED, "dl_sgd_round: the fused momentum round runs on the LDS "
+                                        "tile kernel (plan path 1); this round plans path %d",
+                    pl.pub.path);
+    *plan = pl.pub;
+    return DL_OK;
+}
+
+int dl_sgd_round(const dl_sgd_round_args *args, void *workspace, size_t ws_bytes,
+                 dl_stream_t stream) {
+    dl_mix_plan plan;
+    int rc = dl_sgd_round_plan(args, &plan);
+    if (rc) return rc;
+    const dl_mix_args &m = args->mix;
+    dl::Launches L;
+    char err[dl::kErrLen];
+    rc = dl::shape_round(m, device_cus(), dl::read_knobs(), workspace, ws_bytes, &L, err,
+                         sgd_buf_vec(args));
+    if (rc) return status(rc, err);
+    for (int i = 0; i < L.n; ++i)
+        if (L.l[i].kind != dl::kLaunchTile)
+            return fail(DL_ERR_UNSUPPORTED, "dl_sgd_round: the fused momentum round runs on the "
+                                            "LDS tile kernel (plan path 1) only");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int i = 0; i < L.n; ++i) {
+        const dl::Launch &l = L.l[i];
+        dl::SgdTileArgs q{};
+        q.p = dl::SgdParams{m.lr, args->momentum, args->dampening, args->weight_decay,
+                            args->first ? 1 : 0, args->nesterov ? 1 : 0};
+        if (args->momentum != 0.f) {
+            q.buf = args->buf;
+            q.ldb = args->ldb;
+            dl::tile_stride(l.t.tiled, args->ldb, l.t.n_rows, 4 * l.chunks, &q.bts, &q.brs);
+        }
+        hipError_t e = dl::launch_mix_sgd_tile(l.t, q, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
+        if (e != hipSuccess)
+            return fail(DL_ERR_HIP, "mix_sgd_tile_kernel%s launch: %s (%d)",
+                        l.fast ? "" : " (tail)", hipGetErrorString(e), (int)e);
+    }
+    if (L.after == dl::kAfterZero) return zero_deviation(m.W.n_rows, m.dev_sq, m.dev_max, s);
+    if (L.after == dl::kAfterReduce) {
+        hipError_t e = dl::launch_dev_reduce(L.partial, L.parts, L.rows, m.dev_sq, m.dev_max, s,
+                                             L.max_zeroed);
+        if (e != hipSuccess) return hip_fail(e, "dev_reduce launch");
+    }
+    return DL_OK;
+}
+
 size_t dl_mlp_workspace_bytes(int32_t n_agents) {
     return n_agents > 0 ? dl::mlp_workspace_floats(n_agents) * sizeof(float) : 0;
 }

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "launch.h"   // TileArgs; plan.h: the tile geometry shared with the planner
+#include "sgd_elem.h"  // SgdParams
 
 namespace dl {
 
@@ -31,6 +32,19 @@ hipError_t launch_mix_gather(const TileArgs &a, bool sgd, bool columns, hipStrea
 // 8 B (tail_fmt 2, heads < 5) or weights + u16 rows (1: 6 B)
 hipError_t launch_mix_tile_reg(const TileArgs &a, int chunks, int head, int tail_fmt, bool sgd,
                                bool dev, int grid, int lds, hipStream_t s);
+// The fused momentum-SGD round's tile kernel (mix_sgd.hip) for one launch of a path-1 round
+// shaped by shape_round: TileArgs as for launch_mix_tile (g required, no halo rows, no row set),
+// plus the momentum buffers -- laid out as x, with their FAST-path strides (launch.h
+// tile_stride) -- and the optimizer's parameters.  buf is read only when mu != 0.
+struct SgdTileArgs {
+    float *buf;
+    int64_t ldb;
+    int64_t bts;    // FAST-path tile stride in bytes
+    uint32_t brs;   // FAST-path row stride in bytes
+    SgdParams p;
+};
+hipError_t launch_mix_sgd_tile(const TileArgs &a, const SgdTileArgs &q, int chunks, bool dev,
+                               int grid, int lds_bytes, bool fast, hipStream_t s);
 // K rounds of mixing on LDS-resident tiles (mix_multi.hip); FAST tiles only, no halo rows
 hipError_t launch_mix_multi(const TileArgs &a, int chunks, int rounds, bool sgd, bool dev,
                             int grid, int lds, hipStream_t s);

@@ -6,17 +6,16 @@
 
 namespace dl {
 
+void tile_stride(bool tiled, int64_t ld, int64_t rows, int64_t T, int64_t *ts, uint32_t *rs) {
+    *ts = tiled ? (ld ? ld : rows) * T * 4 : T * 4;
+    *rs = (uint32_t)(tiled ? T * 4 : ld * 4);
+}
+
 namespace {
 
 // MI355X Infinity Cache (MALL), shared by all XCDs
 constexpr size_t kMallBytes = (size_t)256 << 20;
 
-// FAST-path strides of one operand for tiles of T columns; a column-tiled operand's tile stride
-// is its block rows (ld, 0 = its own rows) x T floats
-void tile_stride(bool tiled, int64_t ld, int64_t rows, int64_t T, int64_t *ts, uint32_t *rs) {
-    *ts = tiled ? (ld ? ld : rows) * T * 4 : T * 4;
-    *rs = (uint32_t)(tiled ? T * 4 : ld * 4);
-}
 void set_tile_strides(TileArgs &t, int64_t T) {
     tile_stride(t.tiled, t.ldx, t.n_loc, T, &t.xts, &t.xrs);
     tile_stride(t.tiled, t.ldg, t.n_loc, T, &t.gts, &t.grs);
@@ -85,7 +84,7 @@ void after_reduce(Launches *out, const float *partial, int parts, int rows, bool
 
 }  // namespace
 
-int check_mix_args(const dl_mix_args *a, char *err) {
+int check_mix_args(const dl_mix_args *a, char *err, bool y_may_be_x) {
     if (!a) return fail(err, DL_ERR_INVALID, "dl_mix_round: args is NULL");
     const dl_csr &W = a->W;
     if (W.n_rows <= 0)
@@ -192,7 +191,8 @@ int check_mix_args(const dl_mix_args *a, char *err) {
                      : ((size_t)(rows - 1) * ld + a->n_params) * 4;
     };
     const size_t yb = extent(a->ldy, W.n_rows);
-    if (overlaps(a->x, extent(a->ldx, NL), a->y, yb))
+    const bool in_place = y_may_be_x && a->y == a->x && a->ldy == a->ldx;
+    if (!in_place && overlaps(a->x, extent(a->ldx, NL), a->y, yb))
         return fail(err, DL_ERR_INVALID, "dl_mix_round: y overlaps x");
     if (a->g && overlaps(a->g, extent(a->ldg, NL), a->y, yb))
         return fail(err, DL_ERR_INVALID, "dl_mix_round: y overlaps g");
@@ -276,7 +276,7 @@ TileArgs tile_args(const dl_mix_args &a, const Knobs &k) {
 }
 
 int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_t ws_bytes,
-                Launches *out, char *err) {
+                Launches *out, char *err, bool vec_ok) {
     reset(out);
     Plan pl;
     int rc = plan_mix(a, n_cus, k, &pl, err);
@@ -285,6 +285,7 @@ int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_
     Launch &l = out->l[0];
     l.t = tile_args(a, k);
     TileArgs &t = l.t;
+    if (!vec_ok) t.vec = 0;
     l.sgd = a.g != nullptr;
     l.dev = pl.dev;   // a lagged halo round always writes its deviation partials
     l.mix = true;

@@ -136,14 +136,21 @@ struct Launches {
 };
 
 // Argument check of every round entry point; the texts say dl_mix_round for all of them.
-int check_mix_args(const dl_mix_args *a, char *err);
+// y_may_be_x: y == x with ldy == ldx is accepted (the fused momentum round mixes in place).
+int check_mix_args(const dl_mix_args *a, char *err, bool y_may_be_x = false);
 // The kernels' view of a round's operands: sizes, float4 eligibility, cache policy, halo blocks.
 TileArgs tile_args(const dl_mix_args &a, const Knobs &k);
+// FAST-path strides in bytes of one operand for tiles of T columns: the next tile's row 0 (*ts)
+// and the next row (*rs).  A column-tiled operand's tile stride is its block rows (ld, 0 = its
+// own `rows`) x T floats.
+void tile_stride(bool tiled, int64_t ld, int64_t rows, int64_t T, int64_t *ts, uint32_t *rs);
 
 // The entry points, after check_mix_args: plan (plan.h) and shape.  Each returns a dl_status
 // and, on failure, the dl_last_error() text in err[kErrLen].
+// vec_ok = false: an operand the args do not describe (the fused momentum round's buffers) rules
+// the float4 kernels out
 int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_t ws_bytes,
-                Launches *out, char *err);
+                Launches *out, char *err, bool vec_ok = true);
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err);
 int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,

@@ -265,6 +265,66 @@ def mix_rounds(W: DeviceCsr, X, Y, rounds, G=None, lr=0.0, dev_sq=None, dev_max=
     return True
 
 
+def _sgd_round_args(W, X, Y, G, M, lr, momentum, dampening, weight_decay, nesterov, first,
+                    dev_sq, dev_max, mean, tiled):
+    if W.n_src != W.n_rows or W.n_local != W.n_rows:
+        raise ValueError("sgd_round mixes whole rounds only (no halo rows, no partition row set)")
+    if G is None:
+        raise ValueError("sgd_round needs the gradients G")
+    if momentum != 0.0 and M is None:
+        raise ValueError("momentum needs a buffer M")
+    if tiled is not None:
+        mix = mix_args_tiled(W, tiled[0], tiled[1], X, Y, G, lr, dev_sq, dev_max, mean)
+        ldb = _tiled_ld(M, "M", W.n_rows, tiled[0], tiled[1], W.device) if M is not None else 0
+    else:
+        mix = mix_args(W, X, Y, G, lr, None, dev_sq, dev_max, mean)
+        if M is not None:
+            _check(M, "M", W.n_rows, X.shape[1], W.device)
+        ldb = _ld(M) if M is not None else 0
+    return _lib.DlSgdRoundArgs(mix, _lib.ptr(M), ldb, float(momentum), float(dampening),
+                               float(weight_decay), int(bool(nesterov)), int(bool(first)))
+
+
+def sgd_round_plan(W: DeviceCsr, X, Y, G, M, momentum=0.0, dampening=0.0, weight_decay=0.0,
+                   nesterov=False, deviation=False, tiled=None):
+    """dl_sgd_round_plan: the configuration ``sgd_round`` would run for these operands, or None
+    when the fused momentum round does not take them (a plan path other than 1)."""
+    lib = _lib.load()
+    dummy = torch.empty(1, dtype=torch.float32, device=W.device) if deviation else None
+    args = _sgd_round_args(W, X, Y, G, M, 0.0, momentum, dampening, weight_decay, nesterov, False,
+                           dummy, dummy, None, tiled)
+    plan = _lib.DlMixPlan()
+    rc = lib.dl_sgd_round_plan(ctypes.byref(args), ctypes.byref(plan))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "dl_sgd_round_plan")
+    return {f: getattr(plan, f) for f, _ in plan._fields_}
+
+
+def sgd_round(W: DeviceCsr, X, Y, G, M, lr, momentum=0.0, dampening=0.0, weight_decay=0.0,
+              nesterov=False, first=False, dev_sq=None, dev_max=None, mean=None,
+              workspace: Workspace = None, tiled=None):
+    """One consensus round with the agents' momentum-SGD step fused in, on the current stream
+    (dl_sgd_round): Y = W sgd(X, G, M) [+ deviation of Y], M updated in the same pass --
+    torch.optim.SGD.step of every row, then the mix, bit for bit ``workloads.sgd_step`` into a
+    scratch followed by ``mix_round`` of it.  Y may be X itself (in place).  M (the momentum
+    buffers, laid out as X; None with momentum 0) is not read when ``first``.
+    ``tiled=(n_params, tile_cols)``: X, G, M, Y in the column-tiled layout.  Returns False,
+    launching nothing, when the fused kernel does not take this round (the caller then runs the
+    two launches)."""
+    lib = _lib.load()
+    P = tiled[0] if tiled is not None else X.shape[1]
+    args = _sgd_round_args(W, X, Y, G, M, lr, momentum, dampening, weight_decay, nesterov, first,
+                           dev_sq, dev_max, mean, tiled)
+    workspace = workspace or Workspace(W.device)
+    wp, wn = workspace.ptr_size(lib.dl_mix_workspace_bytes(W.n_rows, 0, P))
+    rc = lib.dl_sgd_round(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc, "dl_sgd_round")
+    return True
+
+
 def trace_max_rounds(W: DeviceCsr, X, Y, tiled=None):
     """dl_mix_trace_plan: the most rounds one traced pass can run, or 0 when the traced kernel
     does not fit this graph/layout (then the caller loops ``mix_round``)."""
@@ -741,6 +801,30 @@ class GossipEngine:
                   dev_max=self.dev_max if deviation else None, mean=mean, workspace=self.ws,
                   tiled=(self.P, self.T) if self.layout == "tiled" else None)
         self.X, self.Y = self.Y, self.X
+
+    def round_sgd(self, G, M, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
+                  first=False, deviation=False, mean=None):
+        """One round with the agents' torch.optim.SGD step fused in: X <- W sgd(X, G, M), M
+        updated (``sgd_round``).  G and M are in the resident layout (``layout_like``); M is None
+        with momentum 0.  Where the fused kernel does not take the round (plan paths 2, 4, 5) it
+        runs as dl_sgd_step into a scratch matrix and ``round(src=scratch)``: the same bits."""
+        tiled = (self.P, self.T) if self.layout == "tiled" else None
+        if sgd_round(self.W, self.X, self.Y, G, M, lr, momentum, dampening, weight_decay, nesterov,
+                     first, dev_sq=self.dev_sq if deviation else None,
+                     dev_max=self.dev_max if deviation else None, mean=mean, workspace=self.ws,
+                     tiled=tiled):
+            self.X, self.Y = self.Y, self.X
+            return
+        from .workloads import sgd_step
+        if getattr(self, "_S", None) is None:
+            self._S = self._empty()
+        # a resident buffer is contiguous and its tile padding is zero (zeros stay zeros under
+        # the step), so the tiled layout is stepped as one row of numel elements
+        flat = (lambda t: t.view(1, -1)) if tiled else (lambda t: t)
+        sgd_step(flat(self.X), flat(G), flat(M) if M is not None else None, out=flat(self._S),
+                 lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                 nesterov=nesterov, first=first)
+        self.round(src=self._S, deviation=deviation, mean=mean)
 
     def trace_max_rounds(self):
         """Most rounds one traced pass (``rounds_traced``) can run; 0 = not supported."""

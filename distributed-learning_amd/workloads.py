@@ -313,14 +313,16 @@ class WRNConsensusSGD:
          S instead of in place;
       3. ``dl_mix_round``: X <- W S with the fused disagreement -- the parameters land back in
          X, so the module views never move and no copy or re-binding is needed.
+    ``fused_round=True`` runs 2 and 3 as one ``dl_sgd_round`` on X in place (the same bits, 20
+    instead of 28 B per element across HBM) and allocates no S.
     Every call is stream-ordered: ``capture()`` records a step as one hipGraph."""
 
     def __init__(self, csr, batch, depth=16, widen=4, dropout=0.0, num_classes=10, lr=0.02,
                  momentum=0.9, weight_decay=5e-4, device="cuda", X0=None, seed=0, streams=1,
-                 deviation=True, data=None, labels=None):
+                 deviation=True, data=None, labels=None, fused_round=False):
         import torch
 
-        from .engine import DeviceCsr, Workspace, plan_shape
+        from .engine import DeviceCsr, Workspace, plan_shape, sgd_round_plan
         from .networks.wide_resnet import Wide_ResNet
         self._torch = torch
         self.device = torch.device(device)
@@ -341,8 +343,14 @@ class WRNConsensusSGD:
         T = plan_shape(self.W, self.P, deviation=True)["tile_cols"] or 1
         self.ld = -(-self.P // max(T, 16)) * max(T, 16)   # zero padding: no ragged tail launch
         f = lambda: torch.zeros(self.N, self.ld, dtype=torch.float32, device=self.device)  # noqa
-        self.X, self.S, self.G = f(), f(), f()
+        self.X, self.G = f(), f()
         self.M = f() if self.momentum != 0.0 else None
+        # fused_round: steps 2 and 3 as one in-place dl_sgd_round on X, no scratch S -- where the
+        # fused kernel takes this graph and shape; else the two launches
+        self.fused_round = bool(fused_round) and sgd_round_plan(
+            self.W, self.X, self.X, self.G, self.M, momentum=self.momentum,
+            weight_decay=self.wd, deviation=self.deviation) is not None
+        self.S = None if self.fused_round else f()
         with torch.no_grad():
             for a, m in enumerate(self.models):
                 if X0 is None:
@@ -396,11 +404,18 @@ class WRNConsensusSGD:
             main.wait_stream(s)
 
     def _round(self, first):
-        from .engine import mix_round
+        from .engine import mix_round, sgd_round
+        dev = dict(dev_sq=self.dev_sq if self.deviation else None,
+                   dev_max=self.dev_max if self.deviation else None, workspace=self.ws)
+        if self.fused_round and sgd_round(self.W, self.X, self.X, self.G, self.M, self.lr,
+                                          momentum=self.momentum, weight_decay=self.wd,
+                                          first=first, **dev):
+            return
+        if self.S is None:   # (the plan at construction took the round: not reached)
+            self.S = self._torch.zeros_like(self.X)
         sgd_step(self.X, self.G, self.M, out=self.S, lr=self.lr, momentum=self.momentum,
                  weight_decay=self.wd, first=first)
-        mix_round(self.W, self.S, self.X, dev_sq=self.dev_sq if self.deviation else None,
-                  dev_max=self.dev_max if self.deviation else None, workspace=self.ws)
+        mix_round(self.W, self.S, self.X, **dev)
 
     def step(self):
         self._local_grads()

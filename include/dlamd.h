@@ -27,6 +27,8 @@
  *                          networks/logreg_model_titanic.py:16-20, + run_round per iteration)
  *   dl_sgd_step, dl_mlp_grad, dl_bgemm, dl_xent_grad <- the per-agent training steps of configs
  *                          c3/c5 (torch.optim.SGD, ANNModel autograd)
+ *   dl_sgd_round        <- torch.optim.SGD.step of every agent and the Mixer._mix_params_once
+ *                          that follows it (Man_Colab.ipynb cells 19-23), in one pass over HBM
  *
  * Conventions
  *   - Every pointer argument is a DEVICE pointer owned by the caller; nothing is allocated inside.
@@ -426,6 +428,36 @@ typedef struct dl_sgd_args {
     int32_t first;                  /* 1: buf = d (torch's first step: clone of the gradient) */
 } dl_sgd_args;
 int dl_sgd_step(const dl_sgd_args *args, dl_stream_t stream);
+
+/* The optimizer step above fused into the consensus round that follows it (config c5: every agent
+ * steps with momentum SGD, then Mixer.mix):  y = W sgd(x, g, buf), buf updated in the same pass.
+ * Bit for bit dl_sgd_step(out = S) followed by dl_mix_round(x = S, g = NULL), for every parameter
+ * setting -- with momentum 0 and weight decay 0 the step is fma(-lr, g, x), dl_sgd_step's
+ * rounding, not dl_mix_round's own fl(x - fl(lr g)) -- but one launch that moves 20 B per element
+ * (read x, g, buf; write buf, y) instead of two that move 28 B, and no scratch matrix S.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   y may be x itself with ldy == ldx (the round in place: a workgroup stages all rows of its
+ *     columns before it writes them); otherwise y must not overlap x.  buf must not overlap x, y
+ *     or g.  Row-major: any n_params >= 1, columns [n_params, ld) of y and buf are never written.
+ *     Column-tiled (mix.tile_cols > 0): buf in the same layout as x, ldb its block rows (0 =
+ *     n_rows), 16-byte aligned operands.
+ *   dev_sq / dev_max / mean describe y as dl_mix_round's do; workspace dl_mix_workspace_bytes.
+ *   LDS tile kernel only: rounds that plan path 2, 4 or 5 return DL_ERR_UNSUPPORTED (the caller
+ *     runs dl_sgd_step + dl_mix_round), as does any halo, partition or lagged-deviation field.
+ *   Stream-ordered, no host synchronisation, no allocation: capturable in a hipGraph.
+ * dl_sgd_round_plan: DL_OK and the configuration the round would run, or the refusal, without
+ * touching the device. */
+typedef struct dl_sgd_round_args {
+    dl_mix_args mix;   /* x, y, W, g (required), lr, n_params, ld*, tile_cols, dev_sq, dev_max, mean;
+                          halo, n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks,
+                          partial_rows_out must be NULL / 0 */
+    float *buf; int64_t ldb;   /* momentum buffers laid out as x (nullable if momentum == 0) */
+    float momentum, dampening, weight_decay;
+    int32_t nesterov, first;   /* as dl_sgd_args */
+} dl_sgd_round_args;
+int dl_sgd_round_plan(const dl_sgd_round_args *args, dl_mix_plan *plan);
+int dl_sgd_round(const dl_sgd_round_args *args, void *workspace, size_t ws_bytes,
+                 dl_stream_t stream);
 
 /* dst[i] = src[i] for n_floats floats (float4 streaming copy; variant 0: one load in flight
  * per thread, 1: eight, 2: eight + non-temporal stores, 3: four + non-temporal loads and
