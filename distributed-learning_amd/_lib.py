@@ -106,6 +106,18 @@ class DlMlpArgs(ctypes.Structure):
                 ("workspace", _vp)]
 
 
+class DlMlpEvalArgs(ctypes.Structure):
+    _fields_ = [("n_agents", _i32), ("rows", _i32), ("input_dim", _i32), ("hidden_dim", _i32),
+                ("output_dim", _i32), ("X", _vp), ("ldx", _i64), ("tile_cols", _i32),
+                ("data", _vp), ("s_data", _i64), ("labels", _vp), ("s_labels", _i64),
+                ("loss", _vp), ("correct", _vp), ("logits", _vp), ("ldz", _i64),
+                ("s_logits", _i64), ("row_splits", _i32)]
+
+
+class DlMlpEvalPlan(ctypes.Structure):
+    _fields_ = [("blocks", _i32), ("row_splits", _i32), ("grid", _i32), ("lds_bytes", _i32)]
+
+
 EPI = {"none": 0, "bias": 1, "bias_relu": 2, "bias_tanh": 3, "bias_elu": 4, "drelu": 5,
        "dtanh": 6, "delu": 7, "bias_xent": 8}
 
@@ -148,6 +160,10 @@ SIGNATURES = {
     "dl_sgd_round": (_i32, [ctypes.POINTER(DlSgdRoundArgs), _vp, _sz, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),
+    "dl_mlp_eval_workspace_bytes": (_sz, [_i32, _i32]),
+    "dl_mlp_eval_plan_query": (_i32, [ctypes.POINTER(DlMlpEvalArgs),
+                                      ctypes.POINTER(DlMlpEvalPlan)]),
+    "dl_mlp_eval": (_i32, [ctypes.POINTER(DlMlpEvalArgs), _vp, _sz, _vp]),
     "dl_bgemm": (_i32, [ctypes.POINTER(DlBgemmArgs), _vp]),
     "dl_xent_grad": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),
     "dl_perron_workspace_bytes": (_sz, [_i32, _i32, _i64]),

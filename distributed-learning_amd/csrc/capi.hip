@@ -820,6 +820,39 @@ int dl_mlp_grad(const dl_mlp_args *a, dl_stream_t stream) {
     return e == hipSuccess ? DL_OK : hip_fail(e, "mlp_fused launch");
 }
 
+size_t dl_mlp_eval_workspace_bytes(int32_t n_agents, int32_t rows) {
+    return dl::eval_workspace_bytes(n_agents, rows);
+}
+
+int dl_mlp_eval_plan_query(const dl_mlp_eval_args *a, dl_mlp_eval_plan *plan) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    int rc = dl::shape_mlp_eval(a, device_cus(), nullptr, 0, false, plan, err);
+    if (rc) return status(rc, err);
+    if (!plan) return fail(DL_ERR_INVALID, "dl_mlp_eval_plan_query: plan is NULL");
+    return DL_OK;
+}
+
+int dl_mlp_eval(const dl_mlp_eval_args *a, void *workspace, size_t ws_bytes, dl_stream_t stream) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    dl_mlp_eval_plan pl;
+    int rc = dl::shape_mlp_eval(a, device_cus(), workspace, ws_bytes, true, &pl, err);
+    if (rc) return status(rc, err);
+    int tsh = 0;
+    while (a->tile_cols > 0 && (1 << tsh) < a->tile_cols) ++tsh;
+    float *part = static_cast<float *>(workspace);
+    int32_t *hit = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) +
+                                               dl::eval_part_bytes(a->n_agents, a->rows));
+    const dl::MlpEvalArgs p{a->X, a->ldx, a->data, a->s_data, a->labels, a->s_labels, part, hit,
+                            a->logits, a->ldz, a->s_logits, a->rows, pl.blocks, pl.row_splits,
+                            a->input_dim, a->hidden_dim, a->output_dim, tsh,
+                            (int64_t)a->n_agents * a->tile_cols};
+    hipError_t e = dl::launch_mlp_eval(p, a->n_agents, a->loss, a->correct,
+                                       static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DL_OK : hip_fail(e, "mlp_eval launch");
+}
+
 int dl_stream_copy(const float *src, float *dst, int64_t n_floats, int32_t variant,
                    dl_stream_t stream) {
     g_err.clear();

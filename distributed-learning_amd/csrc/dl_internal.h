@@ -207,6 +207,28 @@ hipError_t launch_mlp_fused(const float *X, int64_t ldx, const float *data, int6
 // the split gradient path's workspace (dl_mlp_args.workspace), in floats
 size_t mlp_workspace_floats(int n_agents);
 
+// dl_mlp_eval's kernel parameter (mlp_fused.hip mlp_eval_kernel), after launch.h shape_mlp_eval
+struct MlpEvalArgs {
+    const float *X;
+    int64_t ldx;
+    const float *data;
+    int64_t s_data;
+    const int32_t *labels;   // nullable with loss == correct == NULL (logits only)
+    int64_t s_lab;
+    float *part;             // [n_agents][blocks] per-block loss parts (workspace)
+    int32_t *hit;            // [n_agents][blocks] per-block correct counts (workspace)
+    float *logits;           // nullable
+    int64_t ldz, s_logits;
+    int32_t rows, blocks, row_splits;
+    int32_t din, dh, dout;
+    int32_t tsh;             // column-tiled X: log2 of the tile width (0 = row-major)
+    int64_t tstride;         // column-tiled: n_agents * T floats per tile
+};
+// the evaluation launch on n_agents * row_splits workgroups and, with loss or correct, the
+// block-order reduce after it
+hipError_t launch_mlp_eval(const MlpEvalArgs &p, int n_agents, float *loss, int32_t *correct,
+                           hipStream_t s);
+
 // sets dl_last_error()'s message (capi.hip) and returns code: for host-only entry points
 // defined outside capi.hip
 int fail_msg(int code, const char *msg);

@@ -496,4 +496,70 @@ int shape_deviation(const float *x, int64_t ldx, int32_t tile_cols, int32_t n_ro
     return DL_OK;
 }
 
+int shape_mlp_eval(const dl_mlp_eval_args *a, int n_cus, const void *ws, size_t ws_bytes,
+                   bool check_ws, dl_mlp_eval_plan *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_mlp_eval: args is NULL");
+    const int64_t din = a->input_dim, dh = a->hidden_dim, dout = a->output_dim, R = a->rows;
+    // dl_mlp_grad's shape gate without the batch clause
+    if (din <= 0 || din % 4 || dh <= 0 || dh > 152 || dh % 2 || dout <= 0 || dout > 16 || R < 1)
+        return fail(err, DL_ERR_UNSUPPORTED,
+                    "dl_mlp_eval: needs input_dim %% 4 == 0, even hidden_dim <= 152, output_dim "
+                    "<= 16, rows >= 1 (got %d, %d, %d, rows %d)", a->input_dim, a->hidden_dim,
+                    a->output_dim, a->rows);
+    const int64_t P = dh * din + dh + 2 * (dh * dh + dh) + dout * dh + dout;
+    const int32_t T = a->tile_cols;
+    const int64_t N = a->n_agents;
+    if (T < 0 || (T > 0 && (T < 4 || (T & (T - 1)) || (int64_t)T * N > 0x7fffffff)))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: tile_cols must be 0 or a power of two >= 4");
+    if (!a->X || !a->data) return fail(err, DL_ERR_INVALID, "dl_mlp_eval: null X or data");
+    if ((a->loss || a->correct) && !a->labels)
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: loss and correct need labels");
+    if (!a->loss && !a->correct && !a->logits)
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: no output (loss, correct, logits all NULL)");
+    if (N < 1 || N > 65535 || (T == 0 && a->ldx < P))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: bad arguments (agents %d, params %lld, ldx "
+                                         "%lld)", a->n_agents, (long long)P, (long long)a->ldx);
+    if (a->s_data != 0 && (a->s_data < R * din || (a->s_data & 3)))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: s_data must be 0 (shared) or a multiple of "
+                                         "4 >= rows * input_dim (got %lld)", (long long)a->s_data);
+    if (a->labels && a->s_labels != 0 && a->s_labels < R)
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: s_labels must be 0 (shared) or >= rows "
+                                         "(got %lld)", (long long)a->s_labels);
+    if (!aligned16(a->X) || !aligned16(a->data) || (T == 0 && (a->ldx & 3)))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: X and data must be 16-byte aligned with row "
+                                         "strides %% 4 == 0");
+    const size_t tb = T ? (size_t)((P + T - 1) / T) * T * N * 4 : 0;
+    if (T && tb / 4 > 0x7fffffff)   // the kernel addresses an agent's tiled row with 32-bit offsets
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_mlp_eval: tiled X too large for 32-bit offsets");
+    if (a->logits && (a->ldz < dout || (N > 1 && a->s_logits < R * a->ldz)))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: logits need ldz >= output_dim and s_logits "
+                                         ">= rows * ldz (got ldz %lld, s_logits %lld)",
+                    (long long)a->ldz, (long long)a->s_logits);
+    const size_t xb = T ? tb : ((size_t)(N - 1) * a->ldx + P) * 4;
+    const size_t db = ((size_t)(N - 1) * a->s_data + (size_t)(R * din)) * 4;
+    auto hits_input = [&](const void *p, size_t n) {
+        return p && (overlaps(p, n, a->X, xb) || overlaps(p, n, a->data, db));
+    };
+    const size_t zb = a->logits ? ((size_t)(N - 1) * a->s_logits + (size_t)((R - 1) * a->ldz + dout)) * 4
+                                : 0;
+    if (hits_input(a->logits, zb) || hits_input(a->loss, (size_t)N * 4) ||
+        hits_input(a->correct, (size_t)N * 4))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_eval: logits, loss or correct overlaps X or data");
+    const int32_t blocks = eval_blocks(a->rows);
+    int64_t rs = a->row_splits > 0 ? a->row_splits : (n_cus + N - 1) / N;
+    if (rs > blocks) rs = blocks;
+    if (rs < 1) rs = 1;
+    if (N * rs > 0x7fffffff) return fail(err, DL_ERR_INVALID, "dl_mlp_eval: grid too large");
+    if (check_ws) {
+        const size_t need = eval_workspace_bytes(a->n_agents, a->rows);
+        if (!ws_holds(ws, ws_bytes, need))
+            return fail(err, DL_ERR_WORKSPACE, "dl_mlp_eval: needs a 16-byte aligned workspace of "
+                                               "%zu bytes (dl_mlp_eval_workspace_bytes)", need);
+        if (hits_input(ws, need))
+            return fail(err, DL_ERR_INVALID, "dl_mlp_eval: the workspace overlaps X or data");
+    }
+    if (out) *out = dl_mlp_eval_plan{blocks, (int32_t)rs, (int32_t)(N * rs), kMlpLdsBytes};
+    return DL_OK;
+}
+
 }  // namespace dl

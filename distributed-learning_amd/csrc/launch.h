@@ -162,4 +162,24 @@ int shape_deviation(const float *x, int64_t ldx, int32_t tile_cols, int32_t n_ro
                     int64_t n_params, float *mean_out, int n_cus, void *ws, size_t ws_bytes,
                     Launches *out, char *err);
 
+// dl_mlp_eval: rows per block, the LDS of one workgroup (mlp_fused.hip asserts it), and the
+// workspace: [n_agents][blocks] float loss parts, then as many int32 correct counts.
+constexpr int kEvalBlockRows = 64;
+constexpr int kMlpLdsBytes = 156480;
+constexpr int32_t eval_blocks(int32_t rows) {
+    return (int32_t)(((int64_t)rows + kEvalBlockRows - 1) / kEvalBlockRows);
+}
+constexpr size_t eval_part_bytes(int32_t n_agents, int32_t rows) {
+    return align_up((size_t)n_agents * (size_t)eval_blocks(rows) * 4);
+}
+constexpr size_t eval_workspace_bytes(int32_t n_agents, int32_t rows) {
+    return n_agents > 0 && rows > 0 ? 2 * eval_part_bytes(n_agents, rows) : 0;
+}
+// Checks a dl_mlp_eval call and shapes its grid: blocks = ceil(rows / 64); row_splits so that
+// n_agents * row_splits workgroups cover the compute units, at most `blocks`; the caller's hint
+// (args.row_splits > 0) instead, clamped to [1, blocks].  check_ws: the workspace too
+// (dl_mlp_eval; the plan query has none).
+int shape_mlp_eval(const dl_mlp_eval_args *a, int n_cus, const void *ws, size_t ws_bytes,
+                   bool check_ws, dl_mlp_eval_plan *out, char *err);
+
 }  // namespace dl

@@ -1442,6 +1442,366 @@ __global__ void __launch_bounds__(DW_THR, 3) mlp_dw1_kernel(MlpArgs p) {
     compute(nt - 1);
 }
 
+// ---------------------------------------------------------------- evaluation (dl_mlp_eval)
+// ---- layer 1: H1 = relu(x W1^T + b1) for the 64 rows of one block, K = din from HBM: x and W1
+// slices double-buffered in LDS (the H2/H3 space and the staging area, free until layer 2), the
+// next two register-prefetched.  This is mlp_fused_kernel's layer 1, statement for statement, as
+// a function over the block's rows.  (The gradient kernel keeps its inline form: calling this
+// function from it gave the same arithmetic but another instruction schedule and register
+// allocation, which tests/test_kernel_isa.py and the c3 timings pin.  A change to either copy
+// belongs in both.)  xrow(r) is the address of the block's row r for EVERY r in [0, 64): a
+// caller whose block is short clamps r into its rows, so the loads below issue unconditionally
+// and never leave the data; rows [0, nrows) are contiguous from xrow(0) at stride din (the fp32
+// path reads them so, and zeroes the rest).  Ends with layer 2's weights requested into w5.
+template <bool L1X6, bool TILED, typename XRow, typename WSet>
+__device__ __forceinline__ void layer1_forward(const PRow<TILED> &Xr, XRow xrow, int nrows,
+                                               int din, int dh, float *H1, float *H2,
+                                               WSet (&w5)[NSL]) {
+    [[maybe_unused]] const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int o_w1 = 0, o_b1 = dh * din, o_w2 = o_b1 + dh;
+    using PM = ParMat<TILED>;
+    auto mat = [&](const PRow<TILED> &r, int off, int ld) { return PM{r, off, ld}; };
+    if constexpr (L1X6) {
+        // waves 4-7 load and split slices, waves 0-3 run the MFMAs, one barrier per slice; two
+        // images of x and W1 planes across H2, H3 and the staging area (mlp_fused_kernel)
+        constexpr int XPL = MB * BK * 2;                    // 4096 bytes per x plane
+        constexpr int IMGB = 3 * XPL + 3 * L1P_BYTES;       // 43008
+        static_assert(2 * IMGB <= (2 * H_FLOATS + STAGE_FLOATS) * 4, "two L1 images fit");
+        char *img0 = reinterpret_cast<char *>(H2);
+        const int ns = (din + BK - 1) / BK;
+        if (wave >= 4) {
+            const int pt = tid - NTHR / 2;                  // 0..255
+            constexpr int XQ = MB * BK / 4 / (NTHR / 2);    // 2 float4 of x per thread
+            constexpr int WQ = 160 * BK / 4 / (NTHR / 2);   // 5 float4 of W1 per thread
+            f32x4 rx[L1_RING][XQ], rw[L1_RING][WQ];   // L1_RING slices in flight
+            const PM W1 = mat(Xr, o_w1, din);
+            // every load issues unconditionally from a clamped in-range address (rows through
+            // xrow, columns here), so the waits before the LDS stores stay counted
+            auto load = [&](int set, int sl) {
+                const int k0 = sl * BK;
+#pragma unroll
+                for (int i = 0; i < XQ; ++i) {
+                    const int e = pt + i * (NTHR / 2), r = e / 8, c = 4 * (e % 8);
+                    rx[set][i] = *reinterpret_cast<const f32x4 *>(
+                        xrow(r) + (k0 + c < din ? k0 + c : din - 4));
+                }
+#pragma unroll
+                for (int i = 0; i < WQ; ++i) {
+                    const int e = pt + i * (NTHR / 2), r = e / 8, c = 4 * (e % 8);
+                    rw[set][i] = *reinterpret_cast<const f32x4 *>(
+                        W1.at(r < dh ? r : dh - 1, k0 + c < din ? k0 + c : din - 4));
+                }
+            };
+            // the out-of-range lanes are zeroed here, at the registers' only use
+            auto store = [&](int set, int sl, char *img) {
+                const int k0 = sl * BK;
+                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < XQ; ++i) {
+                    const int e = pt + i * (NTHR / 2), r = e / 8, c = 4 * (e % 8);
+                    bf16x4 h, m, l;
+                    split4(k0 + c < din ? rx[set][i] : z, h, m, l);
+                    const uint32_t o = l1_wofs(r, c);
+                    *reinterpret_cast<bf16x4 *>(img + o) = h;
+                    *reinterpret_cast<bf16x4 *>(img + XPL + o) = m;
+                    *reinterpret_cast<bf16x4 *>(img + 2 * XPL + o) = l;
+                }
+                char *wpl = img + 3 * XPL;
+#pragma unroll
+                for (int i = 0; i < WQ; ++i) {
+                    const int e = pt + i * (NTHR / 2), r = e / 8, c = 4 * (e % 8);
+                    bf16x4 h, m, l;
+                    split4(r < dh && k0 + c < din ? rw[set][i] : z, h, m, l);
+                    const uint32_t o = l1_wofs(r, c);
+                    *reinterpret_cast<bf16x4 *>(wpl + o) = h;
+                    *reinterpret_cast<bf16x4 *>(wpl + L1P_BYTES + o) = m;
+                    *reinterpret_cast<bf16x4 *>(wpl + 2 * L1P_BYTES + o) = l;
+                }
+            };
+            // loads past the last slice re-read it; the scheduling barriers keep the first
+            // sets' loads in set order (counted waits at the loop head)
+#pragma unroll
+            for (int j = 0; j < L1_RING; ++j) {
+                load(j, j < ns ? j : ns - 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            for (int s0 = 0; s0 < ns; s0 += L1_RING) {
+#pragma unroll
+                for (int j = 0; j < L1_RING; ++j) {   // register set j holds slice s0 + j
+                    const int sl = s0 + j;
+                    if (sl < ns) store(j, sl, img0 + (sl & 1) * IMGB);
+                    load(j, sl + L1_RING < ns ? sl + L1_RING : ns - 1);
+                    if (sl < ns) __syncthreads();
+                }
+            }
+        } else {
+            // wave c: M-tiles 2 (c & 1), 2 (c & 1) + 1 x N-tiles 5 (c >> 1) .. + 4
+            constexpr int MT = DL_L1_TILING ? 2 : 1, NT = 10 / MT;
+            const int m0 = DL_L1_TILING ? 2 * (wave & 1) : wave, n0 = DL_L1_TILING ? NT * (wave >> 1) : 0;
+            f32x4 acc[MT][NT], sml[MT][NT];
+#pragma unroll
+            for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+                for (int t = 0; t < NT; ++t) acc[mi][t] = sml[mi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            float bv[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int n = 16 * (n0 + t) + (lane & 15);
+                bv[t] = n < dh ? *Xr.at(o_b1 + n) : 0.f;
+            }
+            const int hq = lane >> 4;
+            auto compute = [&](const char *img) {
+                bf16x8 ah[MT], am[MT], al[MT];
+#pragma unroll
+                for (int mi = 0; mi < MT; ++mi) {
+                    const uint32_t oa = l1_wofs(16 * (m0 + mi) + (lane & 15), 8 * hq);
+                    ah[mi] = *reinterpret_cast<const bf16x8 *>(img + oa);
+                    am[mi] = *reinterpret_cast<const bf16x8 *>(img + XPL + oa);
+                    al[mi] = *reinterpret_cast<const bf16x8 *>(img + 2 * XPL + oa);
+                }
+                const char *wpl = img + 3 * XPL;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const uint32_t ob = l1_wofs(16 * (n0 + t) + (lane & 15), 8 * hq);
+                    const bf16x8 bh = *reinterpret_cast<const bf16x8 *>(wpl + ob);
+                    const bf16x8 bm = *reinterpret_cast<const bf16x8 *>(wpl + L1P_BYTES + ob);
+                    const bf16x8 bl = *reinterpret_cast<const bf16x8 *>(wpl + 2 * L1P_BYTES + ob);
+#pragma unroll
+                    for (int mi = 0; mi < MT; ++mi)
+                        mfma_x6(ah[mi], am[mi], al[mi], bh, bm, bl, acc[mi][t], sml[mi][t]);
+                }
+            };
+            for (int sl = 0; sl < ns; ++sl) {
+                if (sl > 0) compute(img0 + ((sl - 1) & 1) * IMGB);
+                __syncthreads();
+            }
+            compute(img0 + ((ns - 1) & 1) * IMGB);
+#pragma unroll
+            for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    acc[mi][t] += sml[mi][t];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = 16 * (m0 + mi) + 4 * hq + r, n = 16 * (n0 + t) + (lane & 15);
+                        if (n < dh) H1[row * LDH + n] = act_fwd(0, acc[mi][t][r] + bv[t]);
+                    }
+                }
+        }
+        load_all_w(w5, mat(Xr, o_w2, dh), dh);   // layer 2's weights
+        __syncthreads();   // every consumer is done with the images before H2/H3 are written
+    } else {
+        f32x4 acc[5];
+        zero(acc);
+        float bv[5];
+        load_bias5(mat(Xr, o_b1, 0), dh, bv);
+        constexpr int IMG = MB * LDS1 + 160 * LDS1;   // one [x | W1] slice image
+        static_assert(2 * IMG <= 2 * H_FLOATS, "two slice images fit the H2/H3 space");
+        struct L1 {
+            RowSlice4<MB> x;
+            RowSlice4<160> w;
+        };
+        pipeline_db<L1>(
+            (din + BK - 1) / BK,
+            [&](L1 &v, int s) {
+                v.x.load(PlainMat{xrow(0), din}, nrows, din, s * BK);
+                v.w.load(mat(Xr, o_w1, din), dh, din, s * BK);
+            },
+            [&](const L1 &v, int buf) {
+                v.x.store(H2 + buf * IMG);
+                v.w.store(H2 + buf * IMG + MB * LDS1);
+            },
+            [&](int s, int buf) {
+                mma_rows64<false>(acc, H2 + buf * IMG, LDS1, H2 + buf * IMG + MB * LDS1);
+            });
+        load_all_w(w5, mat(Xr, o_w2, dh), dh);   // layer 2's weights
+        epi_rows64_t(acc, [&](int m, int n, int t, float v) {
+            if (n < dh) H1[m * LDH + n] = act_fwd(0, v + bv[t]);
+        });
+    }
+}
+
+// Forward only: every agent's test loss, correct count and (optionally) logits.  One workgroup
+// per (agent, row split) walks the agent's 64-row blocks b = split, split + row_splits, ... and
+// runs, per block, the gradient kernel's forward: layer1_forward, forward_hidden_all for layers
+// 2 and 3, the logits MFMA against the W4 image and the 16-lane softmax / cross-entropy head --
+// the same code, so a full block's loss is dl_mlp_grad's loss of those 64 rows bit for bit.  No
+// backward state: no ones columns, no W^T sets, no G.  The weights are re-read per block (from
+// L2 / the MALL after the first).
+// A short last block (rows % 64 != 0): layer 1's loads clamp the row into the block's rows (they
+// stay unconditional and inside `data`), the labels are read from a clamped row too, and the
+// rows past the end are masked in the head (term 0, no hit) and their logits not stored.
+// Per block the workgroup leaves part[a][b] = sum over the block's rows of term_r / 64, in the
+// gradient head's order, and hit[a][b] = the rows whose first maximal logit is the label's (a
+// row with a NaN logit counts as wrong); mlp_eval_reduce_kernel sums them in block order, so
+// the results do not depend on row_splits or the grid.
+// HEAD = false: logits only (no labels are read).
+static_assert(LDS_FLOATS * 4 == kMlpLdsBytes, "launch.h states this file's LDS footprint");
+
+template <bool TILED, bool L1X6, bool HEAD>
+__global__ void __launch_bounds__(NTHR) mlp_eval_kernel(MlpEvalArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *H1 = lds, *H2 = lds + H_FLOATS, *H3 = lds + 2 * H_FLOATS;
+    float *stage = lds + 3 * H_FLOATS;
+    float *Zs = stage + STAGE_FLOATS;
+    float *lpart = Zs + Z_FLOATS;                         // [8] loss parts, then [8] hit counts
+    int *hpart = reinterpret_cast<int *>(lpart) + 8;
+    const int a = blockIdx.x / p.row_splits, split = blockIdx.x - a * p.row_splits;
+    const int dout = p.dout;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    PRow<TILED> Xa;
+    if constexpr (TILED)
+        Xa = {const_cast<float *>(p.X) + ((int64_t)a << p.tsh), (int)p.tstride, p.tsh};
+    else
+        Xa = {const_cast<float *>(p.X) + (int64_t)a * p.ldx, 0, 0};
+    using PM = ParMat<TILED>;
+    PRow<TILED> Xr;
+    auto mat = [&](int off, int ld) { return PM{Xr, off, ld}; };
+    using WSet = std::conditional_t<L1X6, RowPairs, RowSlice<160>>;
+    WSet w5[NSL];
+    // zero all of LDS once (the gradient kernel's reason: K tails read only finite values); a
+    // later block finds the previous block's finite values there instead
+    for (int e = tid; e < LDS_FLOATS / 4; e += NTHR)
+        reinterpret_cast<f32x4 *>(lds)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+    __syncthreads();
+    for (int b = split; b < p.blocks; b += p.row_splits) {
+        // The block's parameter addresses are the same every block; computed once before the
+        // loop (where the compiler moves them, being loop-invariant) they stay live across the
+        // whole body and spill (71-255 registers, against none without the loop).  An empty asm
+        // per block makes the row's base and geometry and the layer sizes opaque, so each phase
+        // forms its addresses where it loads, as in the gradient kernel.
+        Xr = Xa;
+        int din = p.din, dh = p.dh;
+        asm volatile("" : "+s"(Xr.base), "+s"(Xr.tstride), "+s"(Xr.sh), "+s"(din), "+s"(dh));
+        const int o_b1 = dh * din, o_w2 = o_b1 + dh, o_b2 = o_w2 + dh * dh, o_w3 = o_b2 + dh,
+                  o_b3 = o_w3 + dh * dh, o_w4 = o_b3 + dh, o_b4 = o_w4 + dout * dh;
+        const int r0 = b * MB;                            // < rows: no overflow
+        const int nv = min(MB, p.rows - r0);              // the block's rows
+        const float *x = p.data + (int64_t)a * p.s_data + (int64_t)r0 * din;
+        layer1_forward<L1X6>(
+            Xr, [&](int r) { return x + (int64_t)(r < nv ? r : nv - 1) * din; }, nv, din, dh, H1,
+            H2, w5);
+        __syncthreads();
+        forward_hidden_all<L1X6>(mat(o_b2, 0), dh, H1, H2, stage, 1, w5, [&](int sl) {
+            w5[sl].load(mat(o_w3, dh), dh, dh, sl * BK);
+        });
+        __syncthreads();
+        // the logits' operands, issued now so they land while layer 3 runs (gradient kernel)
+        constexpr int W4PER = (16 * LDW4 + NTHR - 1) / NTHR;
+        float w4v[W4PER];
+#pragma unroll
+        for (int i = 0; i < W4PER; ++i) {
+            const int e = tid + i * NTHR;
+            const int n = e / LDW4, k = e % LDW4;
+            w4v[i] = (e < 16 * LDW4 && n < dout && k < dh) ? *Xr.at(o_w4 + n * dh + k) : 0.f;
+        }
+        const float b4v = (lane & 15) < dout ? *Xr.at(o_b4 + (lane & 15)) : 0.f;
+        // this lane's two rows of the head (row wave + 8 i, i = 4 pass + lane / 16); a row past
+        // the block's end reads the last row's label (in range) and is masked below
+        [[maybe_unused]] int lab2[2];
+        if constexpr (HEAD) {
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) {
+                const int m = wave + 8 * (4 * ps + (lane >> 4));
+                lab2[ps] = p.labels[(int64_t)a * p.s_lab + r0 + (m < nv ? m : nv - 1)];
+            }
+        }
+        forward_hidden_all<L1X6>(mat(o_b3, 0), dh, H2, H3, stage, 2, w5, [](int) {});
+        // ---- logits Z = H3 W4^T + b4 (waves 0-3, one 16 x 16 tile each), W4 image [16][LDW4]
+#pragma unroll
+        for (int i = 0; i < W4PER; ++i) {
+            const int e = tid + i * NTHR;
+            if (e < 16 * LDW4) stage[e] = w4v[i];
+        }
+        __syncthreads();
+        if (wave < 4) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            const int m = wave * 16 + (lane & 15);
+#pragma unroll
+            for (int kk = 0; kk < 152; kk += 4) {   // columns dh.. of the W4 image are zero
+                const int k = kk + (lane >> 4);
+                acc = mfma4(H3[m * LDH + k], stage[(lane & 15) * LDW4 + k], acc);
+            }
+            const int n = lane & 15;
+            float *zo = p.logits ? p.logits + (int64_t)a * p.s_logits + (int64_t)r0 * p.ldz
+                                 : nullptr;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = wave * 16 + 4 * (lane >> 4) + r;
+                const float z = acc[r] + b4v;
+                if (n < dout) Zs[row * LDZ + n] = z;
+                if (zo && n < dout && row < nv) zo[(int64_t)row * p.ldz + n] = z;
+            }
+        }
+        __syncthreads();
+        if constexpr (HEAD) {
+            // the gradient kernel's head (same expressions, same order) without dZ4, plus the
+            // argmax: the first class whose logit equals the row maximum
+            const int g = lane >> 4, c = lane & 15;
+            float tq[2];
+            int hq[2];
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) {
+                const int m = wave + 8 * (4 * ps + g);
+                const float v = c < dout ? Zs[m * LDZ + c] : 0.f;
+                float mx = c < dout ? v : -INFINITY;
+                for (int s = 8; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s));
+                const float e = c < dout ? expf(v - mx) : 0.f;
+                float sum = e;
+                for (int s = 8; s >= 1; s >>= 1) sum += __shfl_xor(sum, s);
+                const int label = lab2[ps];
+                const float zl = __shfl(v, 16 * g + label);
+                tq[ps] = m < nv ? (logf(sum) + mx - zl) / (float)MB : 0.f;
+                int first = (c < dout && v == mx) ? c : 16;
+                int nan = (c < dout && v != v) ? 1 : 0;
+                for (int s = 8; s >= 1; s >>= 1) {
+                    first = min(first, __shfl_xor(first, s));
+                    nan |= __shfl_xor(nan, s);
+                }
+                hq[ps] = (m < nv && !nan && first == label) ? 1 : 0;
+            }
+            float lsum = 0.f;
+            int hsum = 0;
+#pragma unroll
+            for (int i = 0; i < MB / 8; ++i) {
+                lsum += __shfl(tq[i / 4], 16 * (i % 4));
+                hsum += __shfl(hq[i / 4], 16 * (i % 4));
+            }
+            if (lane == 0) {
+                lpart[wave] = lsum;
+                hpart[wave] = hsum;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                const int64_t o = (int64_t)a * p.blocks + b;
+                p.part[o] = ((lpart[0] + lpart[1]) + (lpart[2] + lpart[3])) +
+                            ((lpart[4] + lpart[5]) + (lpart[6] + lpart[7]));
+                int h = 0;
+                for (int w = 0; w < 8; ++w) h += hpart[w];
+                p.hit[o] = h;
+            }
+        }
+        __syncthreads();   // the next block's layer 1 overwrites H2, H3 and the staging area
+    }
+}
+
+// loss[a] = (float)((sum_b (double)part[a][b]) * 64 / rows), correct[a] = sum_b hit[a][b], both
+// in block order; one thread per agent
+__global__ void __launch_bounds__(256) mlp_eval_reduce_kernel(const float *part, const int32_t *hit,
+                                                             int n_agents, int blocks, int rows,
+                                                             float *loss, int32_t *correct) {
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_agents) return;
+    double s = 0.0;
+    int32_t h = 0;
+    for (int b = 0; b < blocks; ++b) {
+        s += (double)part[(int64_t)a * blocks + b];
+        h += hit[(int64_t)a * blocks + b];
+    }
+    if (loss) loss[a] = (float)(s * (double)MB / (double)rows);
+    if (correct) correct[a] = h;
+}
+
 }  // namespace
 
 int mlp_fused_supported(int batch, int din, int dh, int dout) {
@@ -1493,6 +1853,35 @@ hipError_t launch_mlp_fused(const float *X, int64_t ldx, const float *data, int6
         return l1_fp32 ? go(mlp_fused_kernel<T, false, false>) : go(mlp_fused_kernel<T, true, false>);
     };
     return tile_cols > 0 ? pick(std::true_type{}) : pick(std::false_type{});
+}
+
+hipError_t launch_mlp_eval(const MlpEvalArgs &p, int n_agents, float *loss, int32_t *correct,
+                           hipStream_t s) {
+    static const bool l1_fp32 = [] {
+        const char *v = getenv("DLAMD_MLP_L1");
+        return v && v[0] == 'f';
+    }();
+    auto go = [&](auto kern) {
+        hipError_t e = allow_full_lds(reinterpret_cast<const void *>(kern));
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(n_agents * p.row_splits)), dim3(NTHR),
+                           LDS_FLOATS * sizeof(float), s, p);
+        return hipGetLastError();
+    };
+    auto pick = [&](auto tiled, auto head) {
+        constexpr bool T = decltype(tiled)::value, H = decltype(head)::value;
+        return l1_fp32 ? go(mlp_eval_kernel<T, false, H>) : go(mlp_eval_kernel<T, true, H>);
+    };
+    const bool head = loss || correct;
+    hipError_t e =
+        p.tsh > 0 ? (head ? pick(std::true_type{}, std::true_type{})
+                          : pick(std::true_type{}, std::false_type{}))
+                  : (head ? pick(std::false_type{}, std::true_type{})
+                          : pick(std::false_type{}, std::false_type{}));
+    if (e != hipSuccess || !head) return e;
+    hipLaunchKernelGGL(mlp_eval_reduce_kernel, dim3((unsigned)((n_agents + 255) / 256)), dim3(256),
+                       0, s, p.part, p.hit, n_agents, p.blocks, p.rows, loss, correct);
+    return hipGetLastError();
 }
 
 }  // namespace dl

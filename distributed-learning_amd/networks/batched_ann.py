@@ -24,6 +24,12 @@ def fused_supported(batch, input_dim, hidden_dim, output_dim):
     return batch == 64 and input_dim % 4 == 0 and 0 < hidden_dim <= 152 and hidden_dim % 2 == 0 and 0 < output_dim <= 16
 
 
+def eval_supported(input_dim, hidden_dim, output_dim):
+    """Shapes the one-launch evaluation (dl_mlp_eval) covers: the gradient kernel's gate without
+    its batch clause -- any number of test rows."""
+    return fused_supported(64, input_dim, hidden_dim, output_dim)
+
+
 class BatchedANN:
     """path: "fused" (dl_mlp_grad: every agent's forward + loss + backward, activations in LDS),
     "layers" (11 dl_bgemm launches) or "auto" (fused when the shapes allow it).
@@ -61,6 +67,7 @@ class BatchedANN:
         self.path = "fused" if (path == "auto" and ok) else ("layers" if path == "auto" else path)
         if split == "auto":
             split = os.environ.get("DLAMD_MLP_SPLIT", "0") == "1"
+        self.eval_out = self.eval_ws = None   # evaluate(): outputs and workspace, on first use
         self.ws = None
         if split and self.path == "fused":
             nb = _lib.load().dl_mlp_workspace_bytes(self.N)
@@ -171,6 +178,125 @@ class BatchedANN:
         self._gemm(dh, din, B, (self.dZa,), dh, hs, 1, (data,), din, B * din, 0,
                    (G, o["fc1.weight"]), din, sg, rowsum=(G, o["fc1.bias"]))
         return self.loss
+
+    # -------------------------------------------------------------- evaluation
+    def evaluate(self, X, data, labels, logits=None, row_splits=0):
+        """Every agent's model on a test set, forward only: returns (loss[N] fp32 mean
+        cross-entropy, correct[N] int32 rows whose logit argmax is the label) -- the per-node
+        ``accuracy ..., loss ...`` of the reference's MasterNode (Man_Colab.ipynb cells 21-23)
+        for all agents in one ``dl_mlp_eval`` launch.  Independent of the training batch size.
+
+        X: as ``gradients`` takes it ([N, P] row-major or the column-tiled [tiles, N, T]);
+        data: fp32 [R, input_dim] (one test set shared by all agents) or [N, R, input_dim];
+        labels: int32 [R] or [N, R] (None with ``logits`` alone: no loss, no count);
+        logits: optional fp32 [N, R, output_dim] output whose last dimension is contiguous (a
+        view of a wider buffer is fine; columns past output_dim are never written);
+        row_splits: workgroups per agent, 0 = chosen; a performance hint, any value gives the
+        same bits.
+
+        The returned tensors are this object's, overwritten by the next call.  Shapes the kernel
+        refuses (``eval_supported``; row-major X only) run the forward as four ``dl_bgemm``
+        launches per row chunk, with the loss and the argmax from torch ops on the logits."""
+        N, din, dh, dout, P = self.N, self.din, self.dh, self.dout, self.P
+        if data.dim() not in (2, 3) or data.shape[-1] != din or data.dtype != torch.float32 or \
+                not data.is_contiguous() or (data.dim() == 3 and data.shape[0] != N):
+            raise ValueError(f"data must be contiguous fp32 [R, {din}] or [{N}, R, {din}]")
+        R = int(data.shape[-2])
+        if R < 1:
+            raise ValueError("data has no rows")
+        s_data = R * din if data.dim() == 3 else 0
+        if labels is None:
+            if logits is None:
+                raise ValueError("nothing to compute: no labels and no logits buffer")
+            s_lab = 0
+        else:
+            if labels.dtype != torch.int32:
+                raise ValueError("labels must be int32")
+            if tuple(labels.shape) not in ((R,), (N, R)) or not labels.is_contiguous():
+                raise ValueError(f"labels must be contiguous int32 [{R}] or [{N}, {R}]")
+            s_lab = R if labels.dim() == 2 else 0
+        if logits is not None and (tuple(logits.shape) != (N, R, dout) or
+                                   logits.dtype != torch.float32 or logits.stride(2) != 1 or
+                                   logits.stride(1) < dout or
+                                   (N > 1 and logits.stride(0) < R * logits.stride(1))):
+            raise ValueError(f"logits must be fp32 [{N}, {R}, {dout}] with a contiguous last "
+                             "dimension and non-overlapping rows")
+        tiled = X.dim() == 3
+        if tiled:
+            tiles, n, T = X.shape
+            if n != N or tiles * T < P or not X.is_contiguous() or X.dtype != torch.float32:
+                raise ValueError(f"expected a contiguous fp32 [tiles, {N}, T] tensor covering "
+                                 f"{P} columns")
+            ldx = 0
+        else:
+            if tuple(X.shape) != (N, P) or X.stride(1) != 1 or X.dtype != torch.float32:
+                raise ValueError(f"expected a row-major fp32 [{N}, {P}] tensor")
+            T, ldx = 0, X.stride(0)
+        if labels is not None and self.eval_out is None:
+            self.eval_out = (torch.empty(N, dtype=torch.float32, device=self.device),
+                             torch.empty(N, dtype=torch.int32, device=self.device))
+        loss, correct = self.eval_out if labels is not None else (None, None)
+        kernel = eval_supported(din, dh, dout) and (
+            tiled or (X.data_ptr() % 16 == 0 and ldx % 4 == 0 and data.data_ptr() % 16 == 0))
+        if not kernel:
+            if tiled:
+                raise ValueError("the column-tiled layout needs shapes dl_mlp_eval covers "
+                                 "(eval_supported)")
+            self._evaluate_layers(X, data, labels, logits, R, loss, correct)
+            return loss, correct
+        lib = _lib.load()
+        need = lib.dl_mlp_eval_workspace_bytes(N, R)
+        if self.eval_ws is None or self.eval_ws.numel() * 4 < need:
+            self.eval_ws = torch.empty(-(-need // 4), dtype=torch.float32, device=self.device)
+        args = _lib.DlMlpEvalArgs(
+            N, R, din, dh, dout, _lib.ptr(X), ldx, T, _lib.ptr(data), s_data, _lib.ptr(labels),
+            s_lab, _lib.ptr(loss), _lib.ptr(correct), _lib.ptr(logits),
+            logits.stride(1) if logits is not None else 0,
+            logits.stride(0) if logits is not None else 0, int(row_splits))
+        _lib.check(lib.dl_mlp_eval(ctypes.byref(args), _lib.ptr(self.eval_ws),
+                                   self.eval_ws.numel() * 4, _lib.stream_handle(self.device)),
+                   "dl_mlp_eval")
+        return loss, correct
+
+    def _evaluate_layers(self, X, data, labels, logits, R, loss, correct):
+        """``evaluate`` for shapes dl_mlp_eval refuses: the forward's four dl_bgemm launches over
+        row chunks (the [N][chunk][hidden] activations at most 64 MiB each; shared data through
+        batch stride 0), loss and argmax by torch on each chunk's logits, summed in fp64."""
+        N, din, dh, dout = self.N, self.din, self.dh, self.dout
+        chunk = max(1, min(R, (1 << 24) // (N * dh)))
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)  # noqa: E731
+        Ha, Hb, Z = f(N, chunk, dh), f(N, chunk, dh), f(N, chunk, dout)
+        sx, o = X.stride(0), self.offsets
+        s_data = R * din if data.dim() == 3 else 0
+        hs, zs = chunk * dh, chunk * dout
+        lsum = torch.zeros(N, dtype=torch.float64, device=self.device)
+        hits = torch.zeros(N, dtype=torch.int64, device=self.device)
+        for r0 in range(0, R, chunk):
+            c = min(chunk, R - r0)
+            self._gemm(c, dh, din, (data, r0 * din), din, s_data, 0, (X, o["fc1.weight"]), din,
+                       sx, 1, (Ha,), dh, hs, "bias_relu", bias=(X, o["fc1.bias"]))
+            self._gemm(c, dh, dh, (Ha,), dh, hs, 0, (X, o["fc2.weight"]), dh, sx, 1,
+                       (Hb,), dh, hs, "bias_tanh", bias=(X, o["fc2.bias"]))
+            self._gemm(c, dh, dh, (Hb,), dh, hs, 0, (X, o["fc3.weight"]), dh, sx, 1,
+                       (Ha,), dh, hs, "bias_elu", bias=(X, o["fc3.bias"]))
+            self._gemm(c, dout, dh, (Ha,), dh, hs, 0, (X, o["fc4.weight"]), dh, sx, 1,
+                       (Z,), dout, zs, "bias", bias=(X, o["fc4.bias"]))
+            z = Z[:, :c]
+            if logits is not None:
+                logits[:, r0:r0 + c] = z
+            if labels is not None:
+                lab = labels[..., r0:r0 + c].long().expand(N, c)
+                zl = z.gather(2, lab.unsqueeze(2)).squeeze(2)
+                lsum += (torch.logsumexp(z, 2) - zl).double().sum(1)
+                hits += (z.argmax(2) == lab).sum(1)
+        if labels is not None:
+            loss.copy_(lsum / R)
+            correct.copy_(hits)
+
+    def eval_flops(self, rows):
+        """Forward FLOPs of ``evaluate`` over ``rows`` test rows per agent."""
+        return self.N * 2 * int(rows) * (self.din * self.dh + 2 * self.dh * self.dh +
+                                        self.dh * self.dout)
 
     def flops_per_step(self):
         B, din, dh, dout = self.B, self.din, self.dh, self.dout

@@ -196,6 +196,35 @@ class MLPConsensusSGD:
         out[self.eng.order] = self.ann.loss
         return out
 
+    def evaluate(self, data, labels, logits=None, row_splits=0):
+        """Every agent's current model on a test set (``BatchedANN.evaluate`` on ``eng.X`` in
+        whichever layout it has): (loss[N], correct[N]) in agent order -- the reference's
+        per-node test statistics (Man_Colab.ipynb cells 21-23).  data: [R, din] shared by all
+        agents or [N, R, din] per agent; labels: int32 [R] or [N, R]; per-agent inputs and the
+        optional logits [N, R, dout] are in agent order too.  Stream-ordered, no host
+        synchronisation: capturable in a hipGraph."""
+        order = self.eng.order
+        if order is not None:      # row s holds agent order[s]
+            if data.dim() == 3:
+                data = data.index_select(0, order.to(data.device))
+            if labels is not None and labels.dim() == 2:
+                labels = labels.index_select(0, order.to(labels.device))
+        rows_logits = logits if order is None or logits is None else \
+            self._torch.empty_like(logits)
+        X = self.eng.X if self.eng.layout == "tiled" else self.eng.X[:, :self.ann.P]
+        loss, correct = self.ann.evaluate(X, data, labels, logits=rows_logits,
+                                          row_splits=row_splits)
+        if order is None:
+            return loss, correct
+        if logits is not None:
+            logits[order] = rows_logits
+        if loss is None:
+            return None, None
+        out = self._torch.empty_like(loss), self._torch.empty_like(correct)
+        out[0][order] = loss
+        out[1][order] = correct
+        return out
+
     @staticmethod
     def padded_params(csr, n_params, device):
         """n_params rounded up to the row-major mix tile width for this graph."""

@@ -29,6 +29,9 @@
  *                          c3/c5 (torch.optim.SGD, ANNModel autograd)
  *   dl_sgd_round        <- torch.optim.SGD.step of every agent and the Mixer._mix_params_once
  *                          that follows it (Man_Colab.ipynb cells 19-23), in one pass over HBM
+ *   dl_mlp_eval         <- MasterNode's per-node test statistics (accuracy and loss of every
+ *                          node on the shared test_loader, Man_Colab.ipynb cells 21-23) through
+ *                          ANNModel.forward (networks/ann_model.py:27-45), all agents at once
  *
  * Conventions
  *   - Every pointer argument is a DEVICE pointer owned by the caller; nothing is allocated inside.
@@ -643,6 +646,56 @@ typedef struct dl_mlp_args {
 } dl_mlp_args;
 size_t dl_mlp_workspace_bytes(int32_t n_agents);   /* (ABI 10) */
 int dl_mlp_grad(const dl_mlp_args *args, dl_stream_t stream);
+
+/* Per-agent evaluation of ANNModel on a test set, forward only, in one launch (plus a tiny
+ * reduce): every agent's mean cross-entropy, its number of correctly classified rows and,
+ * optionally, its logits -- the per-node `accuracy ..., loss ...` that the reference's MasterNode
+ * prints every stat_step from one shared test_loader (Man_Colab.ipynb cells 21-23), i.e.
+ * ANNModel.forward (networks/ann_model.py:27-45) + CrossEntropyLoss + argmax for all agents.
+ * The parameters stay in the engine's resident layout (X as dl_mlp_args: row-major, or
+ * column-tiled with tile_cols > 0); activations stay in LDS.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   Shapes: input_dim % 4 == 0, even hidden_dim <= 152, output_dim <= 16, rows >= 1 (dl_mlp_grad's
+ *     gate without its batch clause); anything else returns DL_ERR_UNSUPPORTED.
+ *   data [rows][input_dim] per agent at stride s_data, labels [rows] int32 at stride s_labels;
+ *     a stride of 0 shares one test set among all agents (the reference's case).  Labels outside
+ *     [0, output_dim) give undefined loss / correct values, never an out-of-bounds access.
+ *   Blocks and the reduce rule.  An agent's rows are cut into blocks of 64; one workgroup per
+ *     (agent, row split) walks blocks split, split + row_splits, ...  Block b leaves in the
+ *     workspace part[a][b] = the sum over its rows of term_r / 64 (term_r = logsumexp(z_r) -
+ *     z_r[label_r], summed in dl_mlp_grad's order: a full block's part is, bit for bit, the loss
+ *     dl_mlp_grad returns for those 64 rows) and hit[a][b] = the rows whose logit argmax is the
+ *     label (first maximum on ties, as torch.argmax; a row with a NaN logit counts as wrong).  A
+ *     second launch then sums in block order, no float atomics:
+ *         loss[a]    = (float)((sum_b (double)part[a][b]) * 64 / rows)
+ *         correct[a] = sum_b hit[a][b]
+ *     so the results do not depend on row_splits or the grid.  Rows past the end of a short last
+ *     block are masked; nothing is read past data or labels, and their logits are not stored.
+ *   logits (nullable) [n_agents][rows][ldz]: columns [output_dim, ldz) are never written.
+ *   X and data 16-byte aligned, ldx and s_data multiples of 4; logits, loss, correct and the
+ *     workspace must not overlap X or data.  workspace: dl_mlp_eval_workspace_bytes(n_agents,
+ *     rows) bytes, 16-byte aligned, else DL_ERR_WORKSPACE.
+ *   Every refusal is decided before any device call.  Stream-ordered, no allocation, no host
+ *     synchronisation: capturable in a hipGraph.
+ * dl_mlp_eval_plan_query: DL_OK and the grid the call would run (blocks = ceil(rows / 64);
+ * row_splits chosen so that n_agents * row_splits workgroups cover the compute units, at most
+ * blocks; a row_splits hint > 0 instead, clamped to [1, blocks]), or the refusal, without
+ * touching the device. */
+typedef struct dl_mlp_eval_args {
+    int32_t n_agents, rows, input_dim, hidden_dim, output_dim;
+    const float *X; int64_t ldx; int32_t tile_cols;     /* as dl_mlp_args */
+    const float *data; int64_t s_data;        /* [rows][input_dim]; agent stride, 0 = shared */
+    const int32_t *labels; int64_t s_labels;  /* [rows]; 0 = shared; nullable iff loss and correct are NULL */
+    float *loss;        /* nullable [n_agents]: mean cross-entropy over the rows */
+    int32_t *correct;   /* nullable [n_agents] */
+    float *logits; int64_t ldz, s_logits;     /* nullable [n_agents][rows][ldz >= output_dim] */
+    int32_t row_splits; /* 0 = choose; a performance hint: any value gives the same bits */
+} dl_mlp_eval_args;
+typedef struct dl_mlp_eval_plan { int32_t blocks, row_splits, grid, lds_bytes; } dl_mlp_eval_plan;
+size_t dl_mlp_eval_workspace_bytes(int32_t n_agents, int32_t rows);
+int dl_mlp_eval_plan_query(const dl_mlp_eval_args *args, dl_mlp_eval_plan *plan);
+int dl_mlp_eval(const dl_mlp_eval_args *args, void *workspace, size_t ws_bytes,
+                dl_stream_t stream);
 
 #ifdef __cplusplus
 }
