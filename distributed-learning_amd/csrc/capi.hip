@@ -853,6 +853,17 @@ int dl_mlp_eval(const dl_mlp_eval_args *a, void *workspace, size_t ws_bytes, dl_
     return e == hipSuccess ? DL_OK : hip_fail(e, "mlp_eval launch");
 }
 
+int dl_batch_gather(const dl_batch_gather_args *a, dl_stream_t stream) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    dl::BatchGatherPlan pl;
+    int rc = dl::shape_batch_gather(a, device_cus(), &pl, err);
+    if (rc) return status(rc, err);
+    hipError_t e = dl::launch_batch_gather(pl, a->advance ? a->cursor : nullptr,
+                                           static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DL_OK : hip_fail(e, "batch_gather launch");
+}
+
 int dl_stream_copy(const float *src, float *dst, int64_t n_floats, int32_t variant,
                    dl_stream_t stream) {
     g_err.clear();

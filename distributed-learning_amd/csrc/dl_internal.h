@@ -229,6 +229,10 @@ struct MlpEvalArgs {
 hipError_t launch_mlp_eval(const MlpEvalArgs &p, int n_agents, float *loss, int32_t *correct,
                            hipStream_t s);
 
+// dl_batch_gather's launches (batch_gather.hip) as launch.h shape_batch_gather shaped them: the
+// gather and, with `advance` (the cursor, writable), the one-thread launch that steps it
+hipError_t launch_batch_gather(const BatchGatherPlan &p, int32_t *advance, hipStream_t s);
+
 // sets dl_last_error()'s message (capi.hip) and returns code: for host-only entry points
 // defined outside capi.hip
 int fail_msg(int code, const char *msg);

@@ -562,4 +562,83 @@ int shape_mlp_eval(const dl_mlp_eval_args *a, int n_cus, const void *ws, size_t 
     return DL_OK;
 }
 
+int shape_batch_gather(const dl_batch_gather_args *a, int n_cus, BatchGatherPlan *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_batch_gather: args is NULL");
+    const int64_t N = a->n_agents, B = a->batch, S = a->steps, D = a->dim, M = a->n_samples;
+    if (N < 1 || B < 1 || S < 1 || M < 1)
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: n_agents, batch, steps and n_samples "
+                                         "must be >= 1 (got %d, %d, %d, %d)", a->n_agents,
+                    a->batch, a->steps, a->n_samples);
+    if (D < 4 || D % 4 || D > (1 << 28))   // a row's bytes are a 32-bit offset in the kernel
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: dim must be a positive multiple of 4, "
+                                         "at most 2^28 (got %d)", a->dim);
+    if (N * B > 0x7fffffff || S * B > 0x7fffffff)
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: n_agents * batch and steps * batch "
+                                         "must be < 2^31");
+    if (!a->samples || !a->index || !a->data)
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: null samples, index or data");
+    if (a->ld_samples < D || (a->ld_samples & 3))
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: ld_samples must be a multiple of 4 >= "
+                                         "dim (got %lld)", (long long)a->ld_samples);
+    if (a->s_data < B * D || (a->s_data & 3))
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: s_data must be a multiple of 4 >= "
+                                         "batch * dim (got %lld)", (long long)a->s_data);
+    if (a->s_index != 0 && a->s_index < S * B)
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: s_index must be 0 (shared) or >= steps "
+                                         "* batch (got %lld)", (long long)a->s_index);
+    if (!aligned16(a->samples) || !aligned16(a->data))
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: samples and data must be 16-byte "
+                                         "aligned");
+    if (a->labels && !a->targets)
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: labels need targets");
+    if (a->labels && a->s_labels < B)
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: s_labels must be >= batch (got %lld)",
+                    (long long)a->s_labels);
+    if (a->advance != 0 && a->advance != 1)
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: advance must be 0 or 1");
+    if (a->advance && !a->cursor)
+        return fail(err, DL_ERR_INVALID, "dl_batch_gather: advance needs a cursor");
+    // no output may share a byte with an input or another output
+    struct Span { const void *p; size_t n; };
+    const Span in[3] = {{a->samples, (size_t)((M - 1) * a->ld_samples + D) * 4},
+                        {a->targets, a->targets ? (size_t)M * 4 : 0},
+                        {a->index, (size_t)((N - 1) * a->s_index + S * B) * 4}};
+    const Span o[3] = {{a->data, (size_t)((N - 1) * a->s_data + B * D) * 4},
+                       {a->labels, a->labels ? (size_t)((N - 1) * a->s_labels + B) * 4 : 0},
+                       {a->cursor, a->cursor ? (size_t)4 : 0}};
+    static const char *const in_name[3] = {"samples", "targets", "index"};
+    static const char *const out_name[3] = {"data", "labels", "cursor"};
+    for (int i = 0; i < 3; ++i) {
+        if (!o[i].n) continue;
+        for (int j = 0; j < 3; ++j)
+            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_batch_gather: %s overlaps %s", out_name[i],
+                            in_name[j]);
+        for (int j = i + 1; j < 3; ++j)
+            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_batch_gather: %s overlaps %s", out_name[i],
+                            out_name[j]);
+    }
+    if (!out) return DL_OK;
+    BatchGatherPlan &p = *out;
+    const int32_t dim4 = (int32_t)(D / 4);
+    p.wide = dim4 >= 64;
+    int sh = 6;
+    if (!p.wide)
+        for (sh = 0; (1 << sh) < dim4; ++sh) {}
+    p.wave_rows = kGatherRowsInFlight * (64 >> sh);
+    const int64_t rows = N * B;
+    const int64_t passes = (rows + p.wave_rows - 1) / p.wave_rows;
+    const int64_t wmax = (int64_t)(n_cus > 0 ? n_cus : 1) * kGatherWavesPerCu;
+    const int64_t waves = passes < wmax ? passes : wmax;
+    const int wpg = kGatherThreads / 64;
+    p.grid = (int32_t)((waves + wpg - 1) / wpg);
+    int64_t st = a->step % S;   // the host step, non-negative
+    if (st < 0) st += S;
+    p.k = BatchGatherArgs{a->samples, a->ld_samples, a->targets, a->index, a->s_index, a->cursor,
+                          a->data, a->s_data, a->labels, a->s_labels, a->n_samples, dim4,
+                          a->batch, a->steps, (int32_t)st, (int32_t)rows, sh};
+    return DL_OK;
+}
+
 }  // namespace dl

@@ -182,4 +182,36 @@ constexpr size_t eval_workspace_bytes(int32_t n_agents, int32_t rows) {
 int shape_mlp_eval(const dl_mlp_eval_args *a, int n_cus, const void *ws, size_t ws_bytes,
                    bool check_ws, dl_mlp_eval_plan *out, char *err);
 
+// dl_batch_gather: the kernel's parameter (batch_gather.hip) and the launch around it.
+struct BatchGatherArgs {
+    const float *samples;
+    int64_t ld_samples;
+    const int32_t *targets;   // nullable with labels
+    const int32_t *index;
+    int64_t s_index;
+    const int32_t *cursor;    // nullable: `step` instead
+    float *data;
+    int64_t s_data;
+    int32_t *labels;          // nullable
+    int64_t s_labels;
+    int32_t n_samples, dim4;  // dim4: float4 chunks per row
+    int32_t batch, steps, step;
+    int32_t rows;             // n_agents * batch destination rows
+    int32_t lane_sh;          // packed rows: log2 of the lanes that share a row (>= dim4 lanes)
+};
+constexpr int kGatherThreads = 256;   // four waves
+constexpr int kGatherRowsInFlight = 4;
+constexpr int kGatherWavesPerCu = 16;
+struct BatchGatherPlan {
+    int32_t wide;      // 1: one wave per row, scalar row base (dim >= 256); 0: rows packed
+    int32_t grid;      // workgroups of kGatherThreads
+    int32_t wave_rows; // destination rows one wave has in flight per pass
+    BatchGatherArgs k;
+};
+// Checks a dl_batch_gather call and shapes its launch.  Rows are dealt to waves in passes of
+// wave_rows = kGatherRowsInFlight rows (wide: one 256-float piece of a row per wave-instruction)
+// or kGatherRowsInFlight * (64 >> lane_sh) rows (packed: dim < 256, 2^lane_sh >= dim / 4 lanes
+// per row), grid-strided over min(passes, n_cus * kGatherWavesPerCu) waves.
+int shape_batch_gather(const dl_batch_gather_args *a, int n_cus, BatchGatherPlan *out, char *err);
+
 }  // namespace dl

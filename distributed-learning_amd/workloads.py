@@ -134,6 +134,176 @@ def accuracy(w, X, y):
     return m.calc_accuracy(X, y)
 
 
+def batch_gather(samples, index, data, targets=None, labels=None, steps=1, cursor=None, step=0,
+                 advance=False, dim=None):
+    """``dl_batch_gather``: with s = (cursor[0] if cursor is given, else step) mod steps,
+    ``data[a, b, :dim] = samples[index[a, s * batch + b], :dim]`` and, with labels,
+    ``labels[a, b] = targets[that id]``; ``advance`` then steps the cursor to (s + 1) mod steps.
+
+    samples: fp32 [n, >= dim] rows (row stride = ld_samples; dim defaults to the row length);
+    targets: int32 [n]; index: int32 [N, steps * batch], or [steps * batch] shared by all agents;
+    data: fp32 [N, batch, dim] whose agent stride may exceed batch * dim; labels: int32
+    [N, batch] whose agent stride may exceed batch; cursor: device int32[1].  Ids outside
+    [0, n) are clamped.  Stream-ordered, no host synchronisation, capturable in a hipGraph."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    dim = int(samples.shape[1] if dim is None else dim)
+    if samples.dim() != 2 or samples.dtype != torch.float32 or samples.stride(1) != 1 or \
+            dim > samples.shape[1]:
+        raise ValueError("samples must be fp32 [n, >= dim] with contiguous rows")
+    if data.dim() != 3 or data.dtype != torch.float32 or data.shape[2] != dim or \
+            data.stride(2) != 1 or data.stride(1) != dim:
+        raise ValueError(f"data must be fp32 [N, batch, {dim}] with contiguous batches")
+    n_agents, batch = int(data.shape[0]), int(data.shape[1])
+    if index.dtype != torch.int32 or index.dim() not in (1, 2) or index.stride(-1) != 1 or \
+            index.shape[-1] != int(steps) * batch or \
+            (index.dim() == 2 and index.shape[0] != n_agents):
+        raise ValueError(f"index must be int32 [{n_agents}, steps * batch] or [steps * batch]")
+    if targets is not None and (targets.dtype != torch.int32 or targets.dim() != 1 or
+                                targets.shape[0] != samples.shape[0] or
+                                not targets.is_contiguous()):
+        raise ValueError("targets must be contiguous int32 [n]")
+    if labels is not None and (labels.dtype != torch.int32 or labels.stride(1) != 1 or
+                               tuple(labels.shape) != (n_agents, batch)):
+        raise ValueError(f"labels must be int32 [{n_agents}, {batch}]")
+    if cursor is not None and (cursor.dtype != torch.int32 or cursor.numel() != 1):
+        raise ValueError("cursor must be one int32")
+    for t in (index, targets, labels, cursor, data):
+        if t is not None and t.device != samples.device:
+            raise ValueError("every operand must live on the samples' device")
+    args = _lib.DlBatchGatherArgs(
+        _lib.ptr(samples), samples.stride(0), _lib.ptr(targets), samples.shape[0], dim,
+        _lib.ptr(index), index.stride(0) if index.dim() == 2 and n_agents > 1 else 0, n_agents,
+        batch, int(steps), _lib.ptr(cursor), int(step), int(bool(advance)), _lib.ptr(data),
+        data.stride(0), _lib.ptr(labels), labels.stride(0) if labels is not None else 0)
+    with torch.cuda.device(samples.device):
+        _lib.check(_lib.load().dl_batch_gather(ctypes.byref(args),
+                                               _lib.stream_handle(samples.device)),
+                   "dl_batch_gather")
+    return data
+
+
+class BatchSampler:
+    """Every agent's ``DataLoader`` over its ``random_split`` shard (Man_Colab.ipynb cell 16),
+    with the dataset resident in HBM: ``next_into`` gathers all agents' next mini-batches in one
+    ``dl_batch_gather`` launch and steps a cursor on the device, so a captured training step
+    walks the epoch with no host work.
+
+    samples: [n, ...] (flattened to fp32 [n, dim], dim % 4 == 0); targets: [n] class ids or
+    None.  shards: one id list per agent; by default the reference's split, ``n // N`` ids each
+    and the remainder to the last agent, cut from a permutation seeded by ``seed``.
+    ``steps = min_a(len(shard_a)) // batch`` batches make an epoch: only full batches are used
+    (the fused gradient kernel needs batch == 64), whereas the reference's ``epoch_len =
+    min(len(loader))`` counts a short last batch too -- an epoch here is one step shorter
+    whenever the smallest shard is no multiple of the batch.
+    ``new_epoch()`` draws a fresh permutation of every shard on the device (``shuffle=True``) and
+    keeps its first steps * batch ids; it rewrites the [N, steps * batch] int32 table in place and
+    zeroes the cursor, so captured graphs stay valid.  ``batch_ids(step)`` are the ids a step
+    uses, in agent order."""
+
+    def __init__(self, samples, targets, n_agents, batch, shards=None, seed=0, device=None):
+        import torch
+        self._torch = torch
+        dev = torch.device(device) if device is not None else (
+            samples.device if samples.is_cuda else torch.device("cuda"))
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        n = int(samples.shape[0])
+        self.n_agents, self.batch = int(n_agents), int(batch)
+        if self.n_agents < 1 or self.batch < 1:
+            raise ValueError("n_agents and batch must be >= 1")
+        self.samples = samples.reshape(n, -1).to(dev, torch.float32).contiguous()
+        self.dim = int(self.samples.shape[1])
+        if self.dim % 4:
+            raise ValueError("the sample length must be a multiple of 4")
+        self.targets = None
+        if targets is not None:
+            if targets.shape != (n,):
+                raise ValueError("targets must be [n]")
+            self.targets = targets.to(dev, torch.int32).contiguous()
+        if shards is None:
+            shards = self.default_shards(n, self.n_agents, seed)
+        shards = [torch.as_tensor(s, dtype=torch.int64).reshape(-1) for s in shards]
+        if len(shards) != self.n_agents:
+            raise ValueError("one shard per agent")
+        for s in shards:
+            if s.numel() and (int(s.min()) < 0 or int(s.max()) >= n):
+                raise ValueError("shard ids must lie in [0, n)")
+        self.shards = shards
+        lens = [int(s.numel()) for s in shards]
+        self.steps = min(lens) // self.batch
+        if self.steps < 1:
+            raise ValueError(f"the smallest shard ({min(lens)} samples) holds no full batch of "
+                             f"{self.batch}")
+        # agent-order shards padded to one length; a padding slot's sort key is +inf, so a
+        # permutation's first len(shard) entries are the shard's own
+        pad = torch.zeros(self.n_agents, max(lens), dtype=torch.int32)
+        for a, s in enumerate(shards):
+            pad[a, :lens[a]] = s.to(torch.int32)
+        self._ids = pad.to(dev)
+        self._is_pad = (torch.arange(max(lens))[None, :] >=
+                        torch.tensor(lens)[:, None]).to(dev)
+        self._gen = torch.Generator(device=dev).manual_seed(int(seed))
+        self.row_agent = None     # table row s holds agent row_agent[s]'s ids (None: agent s's)
+        self.table = torch.zeros(self.n_agents, self.steps * self.batch, dtype=torch.int32,
+                                 device=dev)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.epochs = 0
+        self.new_epoch()
+
+    @staticmethod
+    def default_shards(n, n_agents, seed=0):
+        """The reference's split (cell 16): ``n // n_agents`` ids each, the remainder to the
+        last agent, consecutive runs of a permutation seeded by ``seed``."""
+        import torch
+        perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
+        sizes = [n // n_agents] * n_agents
+        sizes[-1] += n % n_agents
+        return list(torch.split(perm, sizes))
+
+    def attach_order(self, order):
+        """Store agent order[s]'s ids in table row s from now on (an engine row order); the
+        permutations drawn per agent do not change."""
+        torch = self._torch
+        if self.row_agent is not None:
+            raise RuntimeError("the sampler already follows a row order")
+        order = torch.as_tensor(order, dtype=torch.int64, device=self.device)
+        self.table.copy_(self.table.index_select(0, order))
+        self.row_agent = order
+
+    def new_epoch(self):
+        torch = self._torch
+        keys = torch.rand(self._ids.shape, generator=self._gen, device=self.device,
+                          dtype=torch.float64)
+        keys.masked_fill_(self._is_pad, float("inf"))
+        perm = torch.argsort(keys, dim=1)[:, :self.steps * self.batch]
+        ids = torch.gather(self._ids, 1, perm)
+        self.table.copy_(ids if self.row_agent is None else ids.index_select(0, self.row_agent))
+        self.cursor.zero_()
+        self.epochs += 1
+
+    def batch_ids(self, step):
+        """int64 [N, batch]: the sample ids of step ``step`` (mod steps) of the current epoch,
+        row a agent a's."""
+        s = int(step) % self.steps
+        rows = self.table[:, s * self.batch:(s + 1) * self.batch].long()
+        if self.row_agent is None:
+            return rows
+        out = self._torch.empty_like(rows)
+        out[self.row_agent] = rows
+        return out
+
+    def next_into(self, data, labels=None):
+        """Gather the batch the cursor points at into data [N, batch, dim] (and labels
+        [N, batch] int32), rows in table order, then step the cursor."""
+        return batch_gather(self.samples, self.table, data, targets=self.targets, labels=labels,
+                            steps=self.steps, cursor=self.cursor, advance=True)
+
+
 class MLPConsensusSGD:
     """Config c3 (BASELINE.json): every agent trains its own ``ANNModel`` (networks/ann_model.py)
     on its own batch and the agents mix after every local step -- the training loop of the
@@ -151,9 +321,20 @@ class MLPConsensusSGD:
     written.  Every call
     is stream-ordered with no host synchronisation, so ``capture()`` can record a step as a
     hipGraph (two graphs: the engine ping-pongs X/Y) and ``replay()`` then runs steps with one
-    graph launch each instead of ~15 kernel launches from Python."""
+    graph launch each instead of ~15 kernel launches from Python.
 
-    def __init__(self, ann, eng, data, labels, lr, deviation=True, emit="auto"):
+    sampler (a ``BatchSampler``; data and labels are then None): every step trains on the next
+    mini-batch of each agent's shard instead of one fixed batch -- ``step()`` starts with
+    ``sampler.next_into`` (one ``dl_batch_gather`` launch into buffers this object owns, the
+    cursor on the device, so captured graphs walk the epoch by themselves) and ``fit`` runs
+    whole epochs: the reference's ``MasterNode`` loop over every node's ``train_loader``.
+    momentum / weight_decay / dampening / nesterov: the optimizer of Man_Colab.ipynb cell 19
+    (``optim.SGD(momentum=0.9, weight_decay=5e-4)``) through ``GossipEngine.round_sgd`` with
+    momentum buffers ``M``; needs emit="grad", and ``capture()`` then needs one eager step first
+    (the buffers hold the first gradient).  All zero (the default): the plain step x - lr g."""
+
+    def __init__(self, ann, eng, data, labels, lr, deviation=True, emit="auto", sampler=None,
+                 momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False):
         if eng.layout == "tiled" and ann.path != "fused":
             raise ValueError("the layered gradients read X row-major: use GossipEngine("
                              "layout='rows') or the fused kernel")
@@ -161,10 +342,23 @@ class MLPConsensusSGD:
             raise ValueError("engine and model disagree on agents/params")
         import torch
         self.ann, self.eng = ann, eng
+        self.sampler = sampler
+        if sampler is not None:
+            if data is not None or labels is not None:
+                raise ValueError("a sampler provides data and labels: pass None for both")
+            if (sampler.n_agents, sampler.batch, sampler.dim) != (ann.N, ann.B, ann.din) or \
+                    sampler.targets is None or sampler.device != eng.device:
+                raise ValueError("the sampler must hold labelled samples of the model's input "
+                                 "size for the engine's agents, batch and device")
+            # rows of the batch buffers are engine rows: the table follows the row order once
+            if eng.order is not None:
+                sampler.attach_order(eng.order)
+            data = torch.empty(ann.N, ann.B, ann.din, dtype=torch.float32, device=eng.device)
+            labels = torch.empty(ann.N, ann.B, dtype=torch.int32, device=eng.device)
         # an engine row order (GossipEngine(order=...), "auto" on plan-path-5 graphs) stores
         # agent eng.order[s] in row s: every per-agent input follows it, so each row still
         # trains on its own agent's batch (results per agent are those of agent order)
-        if eng.order is not None:
+        elif eng.order is not None:
             data = data.index_select(0, eng.order.to(data.device))
             labels = labels.index_select(0, eng.order.to(labels.device))
         self.data, self.labels = data, labels
@@ -174,6 +368,13 @@ class MLPConsensusSGD:
         if emit not in ("step", "grad") or (emit == "step" and ann.path != "fused"):
             raise ValueError("emit must be 'grad', or 'step' with the fused gradient kernel")
         self.emit = emit
+        self.opt = dict(momentum=float(momentum), dampening=float(dampening),
+                        weight_decay=float(weight_decay), nesterov=bool(nesterov))
+        self.optimizer = momentum != 0.0 or weight_decay != 0.0
+        if self.optimizer and emit != "grad":
+            raise ValueError("momentum / weight_decay need emit='grad'")
+        self.M = torch.zeros_like(eng.X) if momentum != 0.0 else None
+        self.steps_done = 0
         # Row-major engines may carry zero padding columns [ann.P, eng.P) (a whole number of mix
         # tiles: no ragged tail launch); the tiled layout zero-pads its last tile itself.  Padding
         # stays exactly zero -- G is zero there and W 0 = 0 -- and adds exact zeros to the
@@ -243,20 +444,30 @@ class MLPConsensusSGD:
 
     def round(self):
         """The round phase alone (after ``gradients``)."""
-        if self.emit == "step":
+        if self.optimizer:
+            self.eng.round_sgd(self.G, self.M, self.lr, first=self.steps_done == 0,
+                               deviation=self.deviation, **self.opt)
+        elif self.emit == "step":
             self.eng.round(src=self.G, deviation=self.deviation)
         else:
             self.eng.round(G=self.G, lr=self.lr, deviation=self.deviation)
 
     def step(self):
+        if self.sampler is not None:
+            self.sampler.next_into(self.data, self.labels)
         self.gradients()
         self.round()
+        self.steps_done += 1
 
     def capture(self):
         """Record one step per ping-pong parity.  Runs nothing: the engine state afterwards is
-        what it was before."""
+        what it was before (and so are the sampler's cursor and the step count)."""
         torch = self._torch
+        if self.optimizer and self.steps_done == 0:
+            raise RuntimeError("run one eager step before capture(): the first step of "
+                               "momentum SGD differs from the ones a graph replays")
         self.eng.reserve_workspace(self.deviation)
+        done = self.steps_done
         graphs = []
         for _ in range(2):
             g = torch.cuda.CUDAGraph()
@@ -265,12 +476,38 @@ class MLPConsensusSGD:
             graphs.append(g)
         self.graphs = graphs              # two swaps: eng.X is the original buffer again
         self._parity = 0
+        self.steps_done = done
 
     def replay(self, steps=1):
         for _ in range(int(steps)):
             self.graphs[self._parity].replay()
             self._parity ^= 1
             self.eng.X, self.eng.Y = self.eng.Y, self.eng.X
+            self.steps_done += 1
+
+    def fit(self, epochs, stat_step=None, test=None):
+        """``epochs`` epochs over the sampler's shards: per epoch ``sampler.new_epoch()`` and
+        then ``sampler.steps`` steps (graph replays after ``capture()``, else eager steps).
+        Every ``stat_step`` steps, counted from this call's start, ``evaluate(*test)`` -- the
+        reference's per-node statistics every ``stat_step`` -- is appended to the returned
+        history as (step, loss[N], correct[N])."""
+        if self.sampler is None:
+            raise ValueError("fit needs a sampler")
+        if stat_step is not None and (int(stat_step) < 1 or test is None):
+            raise ValueError("stat_step must be >= 1 and needs a test set")
+        history, step = [], 0
+        for _ in range(int(epochs)):
+            self.sampler.new_epoch()
+            for _ in range(self.sampler.steps):
+                if self.graphs is not None:
+                    self.replay()
+                else:
+                    self.step()
+                step += 1
+                if stat_step is not None and step % int(stat_step) == 0:
+                    loss, correct = self.evaluate(*test)
+                    history.append((step, loss.clone(), correct.clone()))
+        return history
 
 
 def _sgd_args(X, G, M, out, lr, momentum, dampening, weight_decay, nesterov, first):

@@ -32,6 +32,8 @@
  *   dl_mlp_eval         <- MasterNode's per-node test statistics (accuracy and loss of every
  *                          node on the shared test_loader, Man_Colab.ipynb cells 21-23) through
  *                          ANNModel.forward (networks/ann_model.py:27-45), all agents at once
+ *   dl_batch_gather     <- every node's next(train_loader) over its random_split shard
+ *                          (Man_Colab.ipynb cells 16, 19-21), from a dataset resident in HBM
  *
  * Conventions
  *   - Every pointer argument is a DEVICE pointer owned by the caller; nothing is allocated inside.
@@ -696,6 +698,45 @@ size_t dl_mlp_eval_workspace_bytes(int32_t n_agents, int32_t rows);
 int dl_mlp_eval_plan_query(const dl_mlp_eval_args *args, dl_mlp_eval_plan *plan);
 int dl_mlp_eval(const dl_mlp_eval_args *args, void *workspace, size_t ws_bytes,
                 dl_stream_t stream);
+
+/* Every agent's next mini-batch gathered by index from a dataset resident in HBM: what each
+ * node's DataLoader over its random_split shard hands the training loop (Man_Colab.ipynb cells
+ * 16, 19-21), for all agents in one launch, with the step inside the epoch kept on the device so
+ * that a replayed hipGraph walks the epoch with no host work.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   With s = (cursor ? cursor[0] : step) mod steps (non-negative, whatever the sign of the
+ *     value):  data[a][b][0:dim] = samples[index[a][s * batch + b]][0:dim]  and, with labels,
+ *     labels[a][b] = targets[that id],  for a < n_agents, b < batch.  index holds ONE epoch's
+ *     sample ids per agent in visiting order; s_index 0 shares one list among all agents.
+ *   A sample id outside [0, n_samples) is clamped into range: the values are then those of row 0
+ *     or n_samples - 1, and nothing is read out of bounds (dl_mlp_eval's convention for labels).
+ *   Elements [batch * dim, s_data) of each agent's data block (the padding between one agent's
+ *     batch and the next) are never written, nor anything of an agent's labels past batch.
+ *   dim % 4 == 0, at most 2^28; ld_samples >= dim and s_data >= batch * dim, both multiples of 4; samples and
+ *     data 16-byte aligned; s_index 0 or >= steps * batch; s_labels >= batch;
+ *     n_agents, batch, steps, n_samples >= 1 and n_agents * batch < 2^31.  advance is 0 or 1;
+ *     advance without cursor, or labels without targets, is refused.  The outputs (data, labels,
+ *     cursor) must not overlap samples, targets, index or each other.  All of these return
+ *     DL_ERR_INVALID, decided before any device call.
+ *   The dataset may be larger than 4 GiB: row bases are 64-bit.
+ *   advance = 1 runs a second, one-thread launch after the gather on the same stream that writes
+ *     cursor[0] = (s + 1) mod steps: every workgroup of the gather reads the same cursor, there
+ *     is no ticket counter and no atomic, and the result is deterministic.
+ *   Stream-ordered, no allocation, no host synchronisation: capturable in a hipGraph. */
+typedef struct dl_batch_gather_args {
+    const float *samples; int64_t ld_samples;  /* [n_samples][ld_samples >= dim] fp32 dataset */
+    const int32_t *targets;                    /* nullable [n_samples] class ids */
+    int32_t n_samples, dim;
+    const int32_t *index; int64_t s_index;     /* [n_agents][steps*batch] sample ids of ONE epoch,
+                                                  in visiting order; agent stride, 0 = shared */
+    int32_t n_agents, batch, steps;
+    int32_t *cursor;                           /* nullable device int32[1]: step inside the epoch */
+    int32_t step;                              /* used when cursor == NULL */
+    int32_t advance;                           /* 1 (needs cursor): cursor <- (s + 1) % steps after the gather */
+    float *data; int64_t s_data;               /* out [n_agents][batch][dim], s_data >= batch*dim */
+    int32_t *labels; int64_t s_labels;         /* out nullable [n_agents][batch]; needs targets */
+} dl_batch_gather_args;
+int dl_batch_gather(const dl_batch_gather_args *args, dl_stream_t stream);
 
 #ifdef __cplusplus
 }
