@@ -126,6 +126,15 @@ class DlBatchGatherArgs(ctypes.Structure):
                 ("s_labels", _i64)]
 
 
+class DlImageBatchArgs(ctypes.Structure):
+    _fields_ = [("samples", _vp), ("ld_samples", _i64), ("targets", _vp), ("n_samples", _i32),
+                ("channels", _i32), ("height", _i32), ("width", _i32), ("lut", _vp),
+                ("index", _vp), ("s_index", _i64), ("aug", _vp), ("s_aug", _i64), ("pad", _i32),
+                ("fill", _i32), ("n_agents", _i32), ("batch", _i32), ("steps", _i32),
+                ("cursor", _vp), ("step", _i32), ("advance", _i32), ("data", _vp),
+                ("s_data", _i64), ("labels", _vp), ("s_labels", _i64)]
+
+
 EPI = {"none": 0, "bias": 1, "bias_relu": 2, "bias_tanh": 3, "bias_elu": 4, "drelu": 5,
        "dtanh": 6, "delu": 7, "bias_xent": 8}
 
@@ -173,6 +182,7 @@ SIGNATURES = {
                                       ctypes.POINTER(DlMlpEvalPlan)]),
     "dl_mlp_eval": (_i32, [ctypes.POINTER(DlMlpEvalArgs), _vp, _sz, _vp]),
     "dl_batch_gather": (_i32, [ctypes.POINTER(DlBatchGatherArgs), _vp]),
+    "dl_image_batch": (_i32, [ctypes.POINTER(DlImageBatchArgs), _vp]),
     "dl_bgemm": (_i32, [ctypes.POINTER(DlBgemmArgs), _vp]),
     "dl_xent_grad": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),
     "dl_perron_workspace_bytes": (_sz, [_i32, _i32, _i64]),

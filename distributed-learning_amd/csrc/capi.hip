@@ -864,6 +864,17 @@ int dl_batch_gather(const dl_batch_gather_args *a, dl_stream_t stream) {
     return e == hipSuccess ? DL_OK : hip_fail(e, "batch_gather launch");
 }
 
+int dl_image_batch(const dl_image_batch_args *a, dl_stream_t stream) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    dl::ImageBatchPlan pl;
+    int rc = dl::shape_image_batch(a, device_cus(), &pl, err);
+    if (rc) return status(rc, err);
+    hipError_t e = dl::launch_image_batch(pl, a->advance ? a->cursor : nullptr,
+                                          static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DL_OK : hip_fail(e, "image_batch launch");
+}
+
 int dl_stream_copy(const float *src, float *dst, int64_t n_floats, int32_t variant,
                    dl_stream_t stream) {
     g_err.clear();

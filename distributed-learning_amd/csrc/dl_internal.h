@@ -233,6 +233,10 @@ hipError_t launch_mlp_eval(const MlpEvalArgs &p, int n_agents, float *loss, int3
 // gather and, with `advance` (the cursor, writable), the one-thread launch that steps it
 hipError_t launch_batch_gather(const BatchGatherPlan &p, int32_t *advance, hipStream_t s);
 
+// dl_image_batch's launches (image_batch.hip) as launch.h shape_image_batch shaped them: the
+// batch and, with `advance` (the cursor, writable), the one-thread launch that steps it
+hipError_t launch_image_batch(const ImageBatchPlan &p, int32_t *advance, hipStream_t s);
+
 // sets dl_last_error()'s message (capi.hip) and returns code: for host-only entry points
 // defined outside capi.hip
 int fail_msg(int code, const char *msg);

@@ -641,4 +641,108 @@ int shape_batch_gather(const dl_batch_gather_args *a, int n_cus, BatchGatherPlan
     return DL_OK;
 }
 
+int shape_image_batch(const dl_image_batch_args *a, int n_cus, ImageBatchPlan *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_image_batch: args is NULL");
+    const int64_t N = a->n_agents, B = a->batch, S = a->steps, M = a->n_samples;
+    const int64_t C = a->channels, H = a->height, W = a->width;
+    if (!a->samples || !a->index || !a->data || !a->lut)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: null samples, index, data or lut");
+    if (N < 1 || B < 1 || S < 1 || M < 1)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: n_agents, batch, steps and n_samples "
+                                         "must be >= 1 (got %d, %d, %d, %d)", a->n_agents,
+                    a->batch, a->steps, a->n_samples);
+    if (H < 1 || W < 1)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: height and width must be >= 1 (got %d, "
+                                         "%d)", a->height, a->width);
+    if (C < 1 || C > kImageMaxChannels)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: channels must lie in [1, %d] (got %d)",
+                    kImageMaxChannels, a->channels);
+    if (W % 4)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: width must be a multiple of 4 (got %d)",
+                    a->width);
+    // an image's bytes and floats are 32-bit offsets in the kernel (H * W < 2^62: no overflow)
+    if (H * W > (1 << 28) || C * H * W > (1 << 28))
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: channels * height * width must be at "
+                                         "most 2^28");
+    const int64_t D = C * H * W;
+    if (a->pad < 0 || a->pad > 127)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: pad must lie in [0, 127] (got %d)",
+                    a->pad);
+    if (a->fill < 0 || a->fill > 255)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: fill must lie in [0, 255] (got %d)",
+                    a->fill);
+    if (N * B > 0x7fffffff || S * B > 0x7fffffff)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: n_agents * batch and steps * batch "
+                                         "must be < 2^31");
+    if (reinterpret_cast<uintptr_t>(a->samples) & 3u)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: samples must be 4-byte aligned");
+    if (a->ld_samples < D || (a->ld_samples & 3))
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: ld_samples must be a multiple of 4 >= "
+                                         "channels * height * width (got %lld)",
+                    (long long)a->ld_samples);
+    if (!aligned16(a->data) || !aligned16(a->lut))
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: data and lut must be 16-byte aligned");
+    if (a->s_data < B * D || (a->s_data & 3))
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: s_data must be a multiple of 4 >= "
+                                         "batch * channels * height * width (got %lld)",
+                    (long long)a->s_data);
+    if (a->s_index != 0 && a->s_index < S * B)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: s_index must be 0 (shared) or >= steps "
+                                         "* batch (got %lld)", (long long)a->s_index);
+    if (a->aug && a->s_aug != 0 && a->s_aug < S * B)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: s_aug must be 0 (shared) or >= steps "
+                                         "* batch (got %lld)", (long long)a->s_aug);
+    if (a->labels && !a->targets)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: labels need targets");
+    if (a->labels && a->s_labels < B)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: s_labels must be >= batch (got %lld)",
+                    (long long)a->s_labels);
+    if (a->advance != 0 && a->advance != 1)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: advance must be 0 or 1");
+    if (a->advance && !a->cursor)
+        return fail(err, DL_ERR_INVALID, "dl_image_batch: advance needs a cursor");
+    // no output may share a byte with an input or another output
+    struct Span { const void *p; size_t n; };
+    const Span in[5] = {{a->samples, (size_t)((M - 1) * a->ld_samples + D)},
+                        {a->targets, a->targets ? (size_t)M * 4 : 0},
+                        {a->index, (size_t)((N - 1) * a->s_index + S * B) * 4},
+                        {a->aug, a->aug ? (size_t)((N - 1) * a->s_aug + S * B) * 4 : 0},
+                        {a->lut, (size_t)C * 256 * 4}};
+    const Span o[3] = {{a->data, (size_t)((N - 1) * a->s_data + B * D) * 4},
+                       {a->labels, a->labels ? (size_t)((N - 1) * a->s_labels + B) * 4 : 0},
+                       {a->cursor, a->cursor ? (size_t)4 : 0}};
+    static const char *const in_name[5] = {"samples", "targets", "index", "aug", "lut"};
+    static const char *const out_name[3] = {"data", "labels", "cursor"};
+    for (int i = 0; i < 3; ++i) {
+        if (!o[i].n) continue;
+        for (int j = 0; j < 5; ++j)
+            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_image_batch: %s overlaps %s", out_name[i],
+                            in_name[j]);
+        for (int j = i + 1; j < 3; ++j)
+            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_image_batch: %s overlaps %s", out_name[i],
+                            out_name[j]);
+    }
+    if (!out) return DL_OK;
+    ImageBatchPlan &p = *out;
+    int sh = 0;
+    while (sh < 6 && (1 << sh) < W / 4) ++sh;
+    p.pass_rows = kImageRowsInFlight * (64 >> sh);
+    p.lds_bytes = (int32_t)(C * 256 * 4);
+    const int64_t images = N * B;
+    const int64_t wmax = (int64_t)(n_cus > 0 ? n_cus : 1) * kImageWavesPerCu;
+    const int64_t waves = images < wmax ? images : wmax;
+    const int wpg = kImageThreads / 64;
+    p.grid = (int32_t)((waves + wpg - 1) / wpg);
+    int64_t st = a->step % S;   // the host step, non-negative
+    if (st < 0) st += S;
+    p.k = ImageBatchArgs{a->samples, a->ld_samples, a->targets, a->lut, a->index, a->s_index,
+                         a->aug, a->s_aug, a->cursor, a->data, a->s_data, a->labels, a->s_labels,
+                         a->n_samples, a->channels, a->height, a->width, a->pad,
+                         (uint32_t)a->fill * 0x01010101u, a->batch, a->steps, (int32_t)st,
+                         (int32_t)images, sh};
+    return DL_OK;
+}
+
 }  // namespace dl

@@ -214,4 +214,43 @@ struct BatchGatherPlan {
 // per row), grid-strided over min(passes, n_cus * kGatherWavesPerCu) waves.
 int shape_batch_gather(const dl_batch_gather_args *a, int n_cus, BatchGatherPlan *out, char *err);
 
+// dl_image_batch: the kernel's parameter (image_batch.hip) and the launch around it.
+struct ImageBatchArgs {
+    const uint8_t *samples;
+    int64_t ld_samples;       // bytes
+    const int32_t *targets;   // nullable with labels
+    const float *lut;         // [channels][256]
+    const int32_t *index;
+    int64_t s_index;
+    const int32_t *aug;       // nullable: the centre crop, no flip
+    int64_t s_aug;
+    const int32_t *cursor;    // nullable: `step` instead
+    float *data;
+    int64_t s_data;
+    int32_t *labels;          // nullable
+    int64_t s_labels;
+    int32_t n_samples, channels, height, width;
+    int32_t pad;
+    uint32_t fill4;           // the fill byte in all four bytes of a dword
+    int32_t batch, steps, step;
+    int32_t images;           // n_agents * batch destination images
+    int32_t lane_sh;          // log2 of the lanes that share an output row (>= width / 4, <= 64)
+};
+constexpr int kImageThreads = 256;   // four waves
+constexpr int kImageRowsInFlight = 4;
+constexpr int kImageWavesPerCu = 16;
+constexpr int kImageMaxChannels = 16;
+struct ImageBatchPlan {
+    int32_t grid;       // workgroups of kImageThreads
+    int32_t lds_bytes;  // the staged table: channels * 256 floats
+    int32_t pass_rows;  // output rows of one channel a wave has in flight per pass
+    ImageBatchArgs k;
+};
+// Checks a dl_image_batch call and shapes its launch.  A wave owns whole destination images (the
+// sample id and the draws are wave-uniform); 2^lane_sh >= width / 4 lanes (at most 64) share an
+// output row, four output pixels each, so a wave-instruction covers 64 >> lane_sh rows and a
+// pass kImageRowsInFlight times as many.  Images are grid-strided over min(images, n_cus *
+// kImageWavesPerCu) waves.
+int shape_image_batch(const dl_image_batch_args *a, int n_cus, ImageBatchPlan *out, char *err);
+
 }  // namespace dl

@@ -186,6 +186,76 @@ def batch_gather(samples, index, data, targets=None, labels=None, steps=1, curso
     return data
 
 
+def image_batch(samples, index, data, lut, aug=None, pad=0, fill=0, targets=None, labels=None,
+                steps=1, cursor=None, step=0, advance=False):
+    """``dl_image_batch``: with s = (cursor[0] if cursor is given, else step) mod steps and
+    id = index[a, s * batch + b], ``data[a, b, c, y, x] = lut[c, P(c, y + top - pad,
+    (W - 1 - x if flip else x) + left - pad)]`` where P is sample id's byte inside the image and
+    ``fill`` outside, (top, left, flip) = bits 0-7, 8-15 and 16 of ``aug[a, s * batch + b]``
+    (aug None: the centre crop, no flip) -- torchvision's pad, crop, flip, ``ToTensor`` +
+    ``Normalize`` with the last two as the table -- and, with labels, ``labels[a, b] =
+    targets[id]``; ``advance`` then steps the cursor to (s + 1) mod steps.
+
+    samples: uint8 [n, C, H, W] planar images (sample stride >= C*H*W, W % 4 == 0); lut: fp32
+    [C, 256]; targets: int32 [n]; index, aug: int32 [N, steps * batch], or [steps * batch] shared
+    by all agents; data: fp32 [N, batch, C, H, W] or [N, batch, C*H*W] whose agent stride may
+    exceed one batch; labels: int32 [N, batch] whose agent stride may exceed batch; cursor:
+    device int32[1].  Ids outside [0, n) and offsets above 2 * pad are clamped.  Stream-ordered,
+    no host synchronisation, capturable in a hipGraph."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    if samples.dim() != 4 or samples.dtype != torch.uint8:
+        raise ValueError("samples must be uint8 [n, C, H, W]")
+    n, C, H, W = (int(v) for v in samples.shape)
+    dim = C * H * W
+    if n < 1 or dim < 1 or samples[0].stride() != (H * W, W, 1) or \
+            (n > 1 and samples.stride(0) < dim):
+        raise ValueError("samples must be uint8 [n, C, H, W] with contiguous planar images")
+    if lut.dtype != torch.float32 or tuple(lut.shape) != (C, 256) or not lut.is_contiguous():
+        raise ValueError(f"lut must be contiguous fp32 [{C}, 256]")
+    if data.dtype != torch.float32 or data.dim() not in (3, 5) or \
+            tuple(data.shape[2:]) not in ((dim,), (C, H, W)) or not data[0].is_contiguous():
+        raise ValueError(f"data must be fp32 [N, batch, {C}, {H}, {W}] or [N, batch, {dim}] "
+                         "with contiguous batches")
+    n_agents, batch = int(data.shape[0]), int(data.shape[1])
+    for name, t in (("index", index), ("aug", aug)):
+        if t is None and name == "aug":
+            continue
+        if t.dtype != torch.int32 or t.dim() not in (1, 2) or t.stride(-1) != 1 or \
+                t.shape[-1] != int(steps) * batch or (t.dim() == 2 and t.shape[0] != n_agents):
+            raise ValueError(f"{name} must be int32 [{n_agents}, steps * batch] or "
+                             "[steps * batch]")
+    if targets is not None and (targets.dtype != torch.int32 or targets.dim() != 1 or
+                                targets.shape[0] != n or not targets.is_contiguous()):
+        raise ValueError("targets must be contiguous int32 [n]")
+    if labels is not None and (labels.dtype != torch.int32 or labels.stride(1) != 1 or
+                               tuple(labels.shape) != (n_agents, batch)):
+        raise ValueError(f"labels must be int32 [{n_agents}, {batch}]")
+    if cursor is not None and (cursor.dtype != torch.int32 or cursor.numel() != 1):
+        raise ValueError("cursor must be one int32")
+    for t in (index, aug, lut, targets, labels, cursor, data):
+        if t is not None and t.device != samples.device:
+            raise ValueError("every operand must live on the samples' device")
+
+    def agent_stride(t):
+        return t.stride(0) if t.dim() == 2 and n_agents > 1 else 0
+    args = _lib.DlImageBatchArgs(
+        _lib.ptr(samples), samples.stride(0) if n > 1 else dim, _lib.ptr(targets), n, C, H, W,
+        _lib.ptr(lut), _lib.ptr(index), agent_stride(index), _lib.ptr(aug),
+        agent_stride(aug) if aug is not None else 0, int(pad), int(fill), n_agents, batch,
+        int(steps), _lib.ptr(cursor), int(step), int(bool(advance)), _lib.ptr(data),
+        data.stride(0) if n_agents > 1 else batch * dim, _lib.ptr(labels),
+        (labels.stride(0) if n_agents > 1 else batch) if labels is not None else 0)
+    with torch.cuda.device(samples.device):
+        _lib.check(_lib.load().dl_image_batch(ctypes.byref(args),
+                                              _lib.stream_handle(samples.device)),
+                   "dl_image_batch")
+    return data
+
+
 class BatchSampler:
     """Every agent's ``DataLoader`` over its ``random_split`` shard (Man_Colab.ipynb cell 16),
     with the dataset resident in HBM: ``next_into`` gathers all agents' next mini-batches in one
@@ -206,20 +276,34 @@ class BatchSampler:
 
     def __init__(self, samples, targets, n_agents, batch, shards=None, seed=0, device=None):
         import torch
+        dev = self._resolve_device(samples, device)
+        n = int(samples.shape[0])
+        self._check_sizes(n_agents, batch)
+        self.samples = samples.reshape(n, -1).to(dev, torch.float32).contiguous()
+        self.dim = int(self.samples.shape[1])
+        if self.dim % 4:
+            raise ValueError("the sample length must be a multiple of 4")
+        self._init_tables(n, targets, shards, seed)
+        self.new_epoch()
+
+    def _resolve_device(self, samples, device):
+        import torch
         self._torch = torch
         dev = torch.device(device) if device is not None else (
             samples.device if samples.is_cuda else torch.device("cuda"))
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
-        n = int(samples.shape[0])
+        return dev
+
+    def _check_sizes(self, n_agents, batch):
         self.n_agents, self.batch = int(n_agents), int(batch)
         if self.n_agents < 1 or self.batch < 1:
             raise ValueError("n_agents and batch must be >= 1")
-        self.samples = samples.reshape(n, -1).to(dev, torch.float32).contiguous()
-        self.dim = int(self.samples.shape[1])
-        if self.dim % 4:
-            raise ValueError("the sample length must be a multiple of 4")
+
+    def _init_tables(self, n, targets, shards, seed):
+        """Targets, shards, the epoch table and the cursor (everything but the samples)."""
+        torch, dev = self._torch, self.device
         self.targets = None
         if targets is not None:
             if targets.shape != (n,):
@@ -253,7 +337,6 @@ class BatchSampler:
                                  device=dev)
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.epochs = 0
-        self.new_epoch()
 
     @staticmethod
     def default_shards(n, n_agents, seed=0):
@@ -304,6 +387,101 @@ class BatchSampler:
                             steps=self.steps, cursor=self.cursor, advance=True)
 
 
+class ImageBatchSampler(BatchSampler):
+    """``BatchSampler`` for a ``uint8`` image dataset under the reference's transforms
+    (Man_Colab.ipynb cell 16): ``RandomCrop(H, padding=pad)``, ``RandomHorizontalFlip()`` (with
+    ``flip``), ``ToTensor()`` and ``Normalize(mean, std)`` -- with pad = 0 and no flip, the test
+    transform.  The dataset stays ``uint8`` in HBM (a quarter of the fp32 copy) and ``next_into``
+    is one ``dl_image_batch`` launch that gathers, crops, flips and converts every agent's next
+    mini-batch to fp32 [N, batch, C, H, W] (or [N, batch, C*H*W]: ``dim`` = C*H*W, so
+    ``MLPConsensusSGD(sampler=...)`` takes it as it takes a ``BatchSampler``).
+
+    Normalisation is the table ``lut[c][v] = (v / 255 - mean[c]) / std[c]`` computed in fp32 as
+    torchvision computes a pixel, so the result equals ``ToTensor`` + ``Normalize`` bit for bit.
+    The random draws are data: ``aug`` is an int32 table shaped like ``table`` (top in bits 0-7,
+    left in bits 8-15, flip in bit 16), and ``new_epoch()`` -- which draws ``table`` exactly as
+    ``BatchSampler`` does for the same seed and shards -- rewrites it in place from a second
+    device generator derived from the seed: top, left ~ U{0..2 * pad}, flip ~ Bernoulli(1/2).
+    ``aug_draws(step)`` are a step's draws in agent order, the twin of ``batch_ids``."""
+
+    _AUG_SEED = 0x5DEECE66D
+
+    def __init__(self, images_u8, targets, n_agents, batch, mean, std, pad=0, flip=False,
+                 shards=None, seed=0, device=None):
+        import torch
+        dev = self._resolve_device(images_u8, device)
+        if images_u8.dim() != 4 or images_u8.dtype != torch.uint8:
+            raise ValueError("images must be uint8 [n, C, H, W]")
+        n, C, H, W = (int(v) for v in images_u8.shape)
+        self._check_sizes(n_agents, batch)
+        if W % 4:
+            raise ValueError("the image width must be a multiple of 4")
+        if not 0 <= int(pad) <= 127:
+            raise ValueError("pad must lie in [0, 127]")
+        self.samples = images_u8.to(dev).contiguous()
+        self.shape, self.dim = (C, H, W), C * H * W
+        self.pad, self.flip, self.fill = int(pad), bool(flip), 0
+        m = torch.as_tensor(mean, dtype=torch.float32).reshape(-1)
+        sd = torch.as_tensor(std, dtype=torch.float32).reshape(-1)
+        if m.numel() != C or sd.numel() != C:
+            raise ValueError("one mean and one std per channel")
+        # ToTensor: byte -> float32 / 255; Normalize: sub_(mean).div_(std), all in fp32
+        self.lut = ((torch.arange(256, dtype=torch.float32).div(255)[None, :] - m[:, None]) /
+                    sd[:, None]).contiguous().to(dev)
+        self._init_tables(n, targets, shards, seed)
+        self._aug_gen = torch.Generator(device=dev).manual_seed(int(seed) ^ self._AUG_SEED)
+        self.aug = torch.zeros_like(self.table)
+        self.new_epoch()
+
+    def attach_order(self, order):
+        """Store agent order[s]'s ids and draws in row s of both tables from now on."""
+        super().attach_order(order)
+        self.aug.copy_(self.aug.index_select(0, self.row_agent))
+
+    def new_epoch(self):
+        torch = self._torch
+        super().new_epoch()
+        shape, kw = tuple(self.table.shape), dict(generator=self._aug_gen, device=self.device,
+                                                  dtype=torch.int32)
+        top = torch.randint(0, 2 * self.pad + 1, shape, **kw)
+        left = torch.randint(0, 2 * self.pad + 1, shape, **kw)
+        words = top | (left << 8)
+        if self.flip:
+            words |= torch.randint(0, 2, shape, **kw) << 16
+        self.aug.copy_(words if self.row_agent is None else
+                       words.index_select(0, self.row_agent))
+
+    def aug_draws(self, step):
+        """(top, left, flip), each int64 [N, batch]: the draws of step ``step`` (mod steps) of
+        the current epoch, row a agent a's."""
+        s = int(step) % self.steps
+        rows = self.aug[:, s * self.batch:(s + 1) * self.batch].long()
+        if self.row_agent is not None:
+            out = self._torch.empty_like(rows)
+            out[self.row_agent] = rows
+            rows = out
+        return rows & 255, (rows >> 8) & 255, (rows >> 16) & 1
+
+    def eval_transform(self, images_u8):
+        """The test transform (``ToTensor`` + ``Normalize``) of uint8 [..., C, H, W] images
+        through the same table: fp32 of the same shape, on the sampler's device."""
+        torch = self._torch
+        C = self.shape[0]
+        x = images_u8.to(self.device)
+        if x.dtype != torch.uint8 or x.dim() < 3 or x.shape[-3] != C:
+            raise ValueError(f"images must be uint8 [..., {C}, H, W]")
+        ch = torch.arange(C, device=self.device).view(C, 1, 1)
+        return self.lut[ch, x.long()]
+
+    def next_into(self, data, labels=None):
+        """Transform the batch the cursor points at into data [N, batch, C, H, W] or
+        [N, batch, C*H*W] (and labels [N, batch] int32), rows in table order, then step the
+        cursor."""
+        return image_batch(self.samples, self.table, data, self.lut, aug=self.aug, pad=self.pad,
+                           fill=self.fill, targets=self.targets, labels=labels,
+                           steps=self.steps, cursor=self.cursor, advance=True)
+
+
 class MLPConsensusSGD:
     """Config c3 (BASELINE.json): every agent trains its own ``ANNModel`` (networks/ann_model.py)
     on its own batch and the agents mix after every local step -- the training loop of the
@@ -323,7 +501,8 @@ class MLPConsensusSGD:
     hipGraph (two graphs: the engine ping-pongs X/Y) and ``replay()`` then runs steps with one
     graph launch each instead of ~15 kernel launches from Python.
 
-    sampler (a ``BatchSampler``; data and labels are then None): every step trains on the next
+    sampler (a ``BatchSampler``, or an ``ImageBatchSampler`` over ``uint8`` images of din bytes;
+    data and labels are then None): every step trains on the next
     mini-batch of each agent's shard instead of one fixed batch -- ``step()`` starts with
     ``sampler.next_into`` (one ``dl_batch_gather`` launch into buffers this object owns, the
     cursor on the device, so captured graphs walk the epoch by themselves) and ``fit`` runs
@@ -581,11 +760,19 @@ class WRNConsensusSGD:
          X, so the module views never move and no copy or re-binding is needed.
     ``fused_round=True`` runs 2 and 3 as one ``dl_sgd_round`` on X in place (the same bits, 20
     instead of 28 B per element across HBM) and allocates no S.
-    Every call is stream-ordered: ``capture()`` records a step as one hipGraph."""
+    Every call is stream-ordered: ``capture()`` records a step as one hipGraph.
+
+    sampler (an ``ImageBatchSampler``; data and labels are then None): every step trains on the
+    next augmented mini-batch of each agent's shard instead of one fixed batch -- the reference's
+    ``train_loader`` under ``transform_train`` (Man_Colab.ipynb cell 16).  ``step()`` then starts
+    with ``sampler.next_into`` (one ``dl_image_batch`` launch into fp32 [N, B, C, H, W] data and
+    int32 labels this object owns, the cursor on the device) and one copy of the labels into the
+    int64 tensor ``F.cross_entropy`` needs, both inside the captured graph, and ``fit`` runs whole
+    epochs."""
 
     def __init__(self, csr, batch, depth=16, widen=4, dropout=0.0, num_classes=10, lr=0.02,
                  momentum=0.9, weight_decay=5e-4, device="cuda", X0=None, seed=0, streams=1,
-                 deviation=True, data=None, labels=None, fused_round=False):
+                 deviation=True, data=None, labels=None, fused_round=False, sampler=None):
         import torch
 
         from .engine import DeviceCsr, Workspace, plan_shape, sgd_round_plan
@@ -633,7 +820,20 @@ class WRNConsensusSGD:
         self.dev_max = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.loss = torch.zeros(self.N, dtype=torch.float32, device=self.device)
         self.ws = Workspace(self.device)
-        if data is None:
+        self.sampler, self.labels32 = sampler, None
+        if sampler is not None:
+            if data is not None or labels is not None:
+                raise ValueError("a sampler provides data and labels: pass None for both")
+            if (sampler.n_agents, sampler.batch) != (self.N, self.B) or \
+                    sampler.targets is None or sampler.device != self.device or \
+                    len(getattr(sampler, "shape", ())) != 3:
+                raise ValueError("the sampler must hold labelled images for this graph's "
+                                 "agents, batch and device")
+            data = torch.empty(self.N, self.B, *sampler.shape, dtype=torch.float32,
+                               device=self.device)
+            self.labels32 = torch.empty(self.N, self.B, dtype=torch.int32, device=self.device)
+            labels = torch.empty(self.N, self.B, dtype=torch.int64, device=self.device)
+        elif data is None:
             g = torch.Generator(device=self.device).manual_seed(seed)
             data = torch.randn(self.N, self.B, 3, 32, 32, device=self.device, generator=g)
             labels = torch.randint(0, num_classes, (self.N, self.B), device=self.device,
@@ -683,14 +883,35 @@ class WRNConsensusSGD:
                  weight_decay=self.wd, first=first)
         mix_round(self.W, self.S, self.X, **dev)
 
+    def _next_batch(self):
+        """With a sampler: every agent's next augmented mini-batch and its int64 labels."""
+        if self.sampler is not None:
+            self.sampler.next_into(self.data, self.labels32)
+            self.labels.copy_(self.labels32)
+
     def step(self):
+        self._next_batch()
         self._local_grads()
         self._round(first=self.steps_done == 0)
         self.steps_done += 1
 
+    def fit(self, epochs):
+        """``epochs`` epochs over the sampler's shards: per epoch ``sampler.new_epoch()`` and
+        then ``sampler.steps`` steps (graph replays after ``capture()``, else eager steps)."""
+        if self.sampler is None:
+            raise ValueError("fit needs a sampler")
+        for _ in range(int(epochs)):
+            self.sampler.new_epoch()
+            for _ in range(self.sampler.steps):
+                if self.graph is not None:
+                    self.replay()
+                else:
+                    self.step()
+
     def capture(self):
         """Record one step (after at least one eager step: the momentum buffers exist and every
-        MIOpen solution is found) as a hipGraph.  Runs nothing."""
+        MIOpen solution is found) as a hipGraph.  Runs nothing (the sampler's cursor stays where
+        it is)."""
         torch = self._torch
         if self.steps_done == 0:
             raise RuntimeError("run one eager step before capture()")
@@ -698,6 +919,7 @@ class WRNConsensusSGD:
         self.ws.get(_lib.load().dl_mix_workspace_bytes(self.N, 0, self.ld))
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
+            self._next_batch()
             self._local_grads()
             self._round(first=False)
         self.graph = g

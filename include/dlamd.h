@@ -34,6 +34,9 @@
  *                          ANNModel.forward (networks/ann_model.py:27-45), all agents at once
  *   dl_batch_gather     <- every node's next(train_loader) over its random_split shard
  *                          (Man_Colab.ipynb cells 16, 19-21), from a dataset resident in HBM
+ *   dl_image_batch      <- transform_train / transform_test of Man_Colab.ipynb cell 16
+ *                          (RandomCrop(32, padding=4), RandomHorizontalFlip, ToTensor, Normalize)
+ *                          on every node's next uint8 mini-batch, draws supplied by the caller
  *
  * Conventions
  *   - Every pointer argument is a DEVICE pointer owned by the caller; nothing is allocated inside.
@@ -737,6 +740,61 @@ typedef struct dl_batch_gather_args {
     int32_t *labels; int64_t s_labels;         /* out nullable [n_agents][batch]; needs targets */
 } dl_batch_gather_args;
 int dl_batch_gather(const dl_batch_gather_args *args, dl_stream_t stream);
+
+/* Every agent's next mini-batch of a planar uint8 image dataset, gathered by sample id, cropped
+ * from its padded image at the caller's per-sample offset, flipped, and mapped byte by byte
+ * through a per-channel table to fp32 NCHW: transform_train of Man_Colab.ipynb cell 16
+ * (RandomCrop(H, padding=pad), RandomHorizontalFlip, ToTensor, Normalize) -- and, without aug,
+ * transform_test -- for all agents in one launch, the epoch cursor on the device as
+ * dl_batch_gather keeps it.  There is no random number generator in the kernel: the draws are
+ * data (aug), one word per (agent, position in the epoch), beside index.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   With s = (cursor ? cursor[0] : step) mod steps (non-negative, whatever the sign of the
+ *     value), for a < n_agents, b < batch:  id = index[a * s_index + s * batch + b] clamped into
+ *     [0, n_samples) (the values are then those of sample 0 or n_samples - 1, and nothing is read
+ *     out of bounds), and with labels  labels[a][b] = targets[id].  index holds ONE epoch's sample
+ *     ids per agent in visiting order; s_index 0 shares one list among all agents.
+ *   The aug word of destination image (a, b) is aug[a * s_aug + s * batch + b] (s_aug 0 shares
+ *     one list): bits 0-7 top, bits 8-15 left, bit 16 flip; higher bits are ignored; top and left
+ *     are clamped to [0, 2 * pad].  aug == NULL: top = left = pad and no flip -- the test
+ *     transform, and with pad = 0 a plain convert.
+ *   data[a][b][c][y][x] = lut[c][ P(c, y + top - pad, (flip ? width - 1 - x : x) + left - pad) ]
+ *     for c < channels, y < height, x < width, where P(c, i, j) is byte
+ *     samples[id * ld_samples + (c * height + i) * width + j] when 0 <= i < height and
+ *     0 <= j < width, and `fill` elsewhere.  This is torchvision's order: pad the bytes with
+ *     `fill`, crop at (top, left), flip the crop, then convert; a border pixel is lut[c][fill],
+ *     not 0.  The kernel copies table entries: the result is exact.
+ *   Nothing is read outside [samples, samples + (n_samples - 1) * ld_samples + C*H*W) whatever
+ *     the ids and offsets.  Elements [batch * C*H*W, s_data) of each agent's data block are never
+ *     written, nor anything of an agent's labels past batch.
+ *   Refused with DL_ERR_INVALID, each with its own message, before any device call: null
+ *     samples, index, data or lut; n_agents, batch, steps, n_samples, height or width < 1;
+ *     channels outside [1, 16]; width % 4 != 0; C*H*W > 2^28; pad outside [0, 127]; fill outside
+ *     [0, 255]; samples not 4-byte aligned; ld_samples % 4 != 0 or < C*H*W; data or lut not
+ *     16-byte aligned; s_data % 4 != 0 or < batch * C*H*W; s_index, or s_aug with aug, neither 0
+ *     nor >= steps * batch; with labels, s_labels < batch; labels without targets; advance
+ *     without cursor; advance not 0 or 1; n_agents * batch or steps * batch >= 2^31; any output
+ *     (data, labels, cursor) sharing a byte with an input (samples, targets, index, aug, lut) or
+ *     with another output -- exact extents: operands that touch do not overlap.
+ *   The dataset may be larger than 4 GiB: row bases are 64-bit.
+ *   advance = 1 runs a second, one-thread launch after the first on the same stream that writes
+ *     cursor[0] = (s + 1) mod steps, as dl_batch_gather does.
+ *   Stream-ordered, no allocation, no host synchronisation: capturable in a hipGraph. */
+typedef struct dl_image_batch_args {
+    const uint8_t *samples; int64_t ld_samples; /* [n_samples][ld_samples >= C*H*W] bytes, planar
+                                                   [C][H][W] per sample; ld_samples in bytes */
+    const int32_t *targets;                     /* nullable [n_samples] */
+    int32_t n_samples, channels, height, width;
+    const float *lut;                           /* [channels][256] fp32: out = lut[c][byte] */
+    const int32_t *index; int64_t s_index;      /* as dl_batch_gather */
+    const int32_t *aug;   int64_t s_aug;        /* nullable, same shape/positions as index; s_aug 0 = shared */
+    int32_t pad, fill;                          /* `fill`-byte border of `pad` pixels on every side */
+    int32_t n_agents, batch, steps;
+    int32_t *cursor; int32_t step; int32_t advance;   /* as dl_batch_gather */
+    float *data; int64_t s_data;                /* out [n_agents][batch][C][H][W], s_data >= batch*C*H*W */
+    int32_t *labels; int64_t s_labels;          /* out nullable; needs targets */
+} dl_image_batch_args;
+int dl_image_batch(const dl_image_batch_args *args, dl_stream_t stream);
 
 #ifdef __cplusplus
 }
