@@ -135,6 +135,13 @@ class DlImageBatchArgs(ctypes.Structure):
                 ("s_data", _i64), ("labels", _vp), ("s_labels", _i64)]
 
 
+class DlLenetArgs(ctypes.Structure):
+    _fields_ = [("n_agents", _i32), ("batch", _i32), ("num_classes", _i32), ("X", _vp),
+                ("ldx", _i64), ("data", _vp), ("s_data", _i64), ("labels", _vp),
+                ("s_labels", _i64), ("G", _vp), ("ldg", _i64), ("loss", _vp), ("logits", _vp),
+                ("ldz", _i64), ("s_logits", _i64)]
+
+
 EPI = {"none": 0, "bias": 1, "bias_relu": 2, "bias_tanh": 3, "bias_elu": 4, "drelu": 5,
        "dtanh": 6, "delu": 7, "bias_xent": 8}
 
@@ -183,6 +190,11 @@ SIGNATURES = {
     "dl_mlp_eval": (_i32, [ctypes.POINTER(DlMlpEvalArgs), _vp, _sz, _vp]),
     "dl_batch_gather": (_i32, [ctypes.POINTER(DlBatchGatherArgs), _vp]),
     "dl_image_batch": (_i32, [ctypes.POINTER(DlImageBatchArgs), _vp]),
+    "dl_lenet_param_count": (_i32, [_i32]),
+    "dl_lenet_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dl_lenet_grad": (_i32, [ctypes.POINTER(DlLenetArgs), _vp, _sz, _vp]),
+    "dl_lenet_grad_events": (_i32, [ctypes.POINTER(DlLenetArgs), _vp, _sz, _vp,
+                                    ctypes.POINTER(_vp), _i32, ctypes.POINTER(_i32)]),
     "dl_bgemm": (_i32, [ctypes.POINTER(DlBgemmArgs), _vp]),
     "dl_xent_grad": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),
     "dl_perron_workspace_bytes": (_sz, [_i32, _i32, _i64]),

@@ -875,6 +875,128 @@ int dl_image_batch(const dl_image_batch_args *a, dl_stream_t stream) {
     return e == hipSuccess ? DL_OK : hip_fail(e, "image_batch launch");
 }
 
+int32_t dl_lenet_param_count(int32_t num_classes) { return dl::lenet_param_count(num_classes); }
+
+size_t dl_lenet_workspace_bytes(int32_t n_agents, int32_t batch, int32_t num_classes) {
+    return dl::lenet_workspace(n_agents, batch, num_classes).total;
+}
+
+namespace {
+// dl_lenet_grad's launches in order; with events, one recorded before each and one after the last
+int lenet_run(const dl_lenet_args *a, void *workspace, size_t ws_bytes, hipStream_t s,
+              void *const *events, int32_t n_events, int32_t *n_launches) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    dl::LenetPlan pl;
+    int rc = dl::shape_lenet(a, device_cus(), workspace, ws_bytes, &pl, err);
+    if (rc) return status(rc, err);
+    if (n_launches) *n_launches = pl.n_launches;
+    if (events && n_events < pl.n_launches + 1)
+        return fail(DL_ERR_INVALID, "dl_lenet_grad_events: needs %d events (got %d)",
+                    pl.n_launches + 1, n_events);
+    const int32_t N = a->n_agents, B = a->batch, nc = a->num_classes;
+    char *ws = static_cast<char *>(workspace);
+    auto f = [&](size_t off) { return reinterpret_cast<float *>(ws + off); };
+    float *pool2 = f(pl.ws.pool2), *h1 = f(pl.ws.h1), *h2 = f(pl.ws.h2), *z = f(pl.ws.z);
+    float *dz3 = f(pl.ws.dz3), *dz2 = f(pl.ws.dz2), *dz1 = f(pl.ws.dz1), *da = f(pl.ws.da);
+    const dl::LenetConvArgs cv{a->X, a->ldx, a->data, a->s_data, f(pl.ws.pool1),
+                               reinterpret_cast<uint8_t *>(ws + pl.ws.code1), pool2,
+                               reinterpret_cast<uint8_t *>(ws + pl.ws.code2), da, f(pl.ws.part),
+                               a->G, a->ldg, B, pl.train, pl.passes, pl.fwd_wpa, pl.groups,
+                               pl.bwd_wpa};
+    int n = 0;
+    hipError_t e = hipSuccess;
+    auto mark = [&]() {   // before a launch (and after the last)
+        if (events && e == hipSuccess) e = hipEventRecord(static_cast<hipEvent_t>(events[n]), s);
+        ++n;
+    };
+    // C[b] (M x Nn) = op(A) op(B) per agent; operands with their row and agent strides
+    auto gemm = [&](int M, int Nn, int K, const float *A, int64_t lda, int64_t sA, int ta,
+                    const float *Bm, int64_t ldb, int64_t sB, int tb, float *C, int64_t ldc,
+                    int64_t sC, int epi, const float *bias, const float *H, int64_t ldh,
+                    float *rowsum, bool xent_loss) {
+        mark();
+        if (e != hipSuccess) return;
+        dl::BgemmArgs p{};
+        p.batch = N; p.M = M; p.N = Nn; p.K = K;
+        p.A = A; p.lda = lda; p.sA = sA; p.ta = ta;
+        p.B = Bm; p.ldb = ldb; p.sB = sB; p.tb = tb;
+        p.C = C; p.ldc = ldc; p.sC = sC;
+        p.epi = epi; p.bias = bias; p.sBias = a->ldx;
+        p.H = H; p.ldh = ldh; p.sH = (int64_t)B * ldh;
+        p.rowsum = rowsum; p.sR = a->ldg;
+        if (epi == dl::EPI_BIAS_XENT) {
+            p.labels = a->labels; p.sLab = a->s_labels;
+            p.loss = xent_loss ? a->loss : nullptr;
+        }
+        e = dl::launch_bgemm(p, s);
+    };
+    const float *X = a->X;
+    float *G = a->G;
+    const int64_t ldx = a->ldx, ldg = a->ldg;
+    const int F1 = dl::kLenetFc1, F2 = dl::kLenetFc2, P2 = dl::kLenetPool2;
+    const int64_t fc3b = dl::kLenetFc3W + 84 * (int64_t)nc;
+    mark();
+    if (e == hipSuccess) e = dl::launch_lenet_conv_fwd(cv, pl.fwd_grid, s);
+    gemm(B, F1, P2, pool2, P2, (int64_t)B * P2, 0, X + dl::kLenetFc1W, P2, ldx, 1, h1, F1,
+         (int64_t)B * F1, dl::EPI_BIAS_RELU, X + dl::kLenetFc1B, nullptr, 0, nullptr, false);
+    gemm(B, F2, F1, h1, F1, (int64_t)B * F1, 0, X + dl::kLenetFc2W, F1, ldx, 1, h2, F2,
+         (int64_t)B * F2, dl::EPI_BIAS_RELU, X + dl::kLenetFc2B, nullptr, 0, nullptr, false);
+    if (a->logits)
+        gemm(B, nc, F2, h2, F2, (int64_t)B * F2, 0, X + dl::kLenetFc3W, F2, ldx, 1, a->logits,
+             a->ldz, a->s_logits, dl::EPI_BIAS, X + fc3b, nullptr, 0, nullptr, false);
+    if (pl.head == 1) {
+        gemm(B, nc, F2, h2, F2, (int64_t)B * F2, 0, X + dl::kLenetFc3W, F2, ldx, 1, dz3, nc,
+             (int64_t)B * nc, dl::EPI_BIAS_XENT, X + fc3b, nullptr, 0, nullptr, true);
+    } else if (pl.head == 2) {
+        gemm(B, nc, F2, h2, F2, (int64_t)B * F2, 0, X + dl::kLenetFc3W, F2, ldx, 1, z, nc,
+             (int64_t)B * nc, dl::EPI_BIAS, X + fc3b, nullptr, 0, nullptr, false);
+        mark();
+        if (e == hipSuccess)
+            e = dl::launch_xent_grad(z, (int64_t)B * nc, a->labels, a->s_labels, dz3,
+                                     (int64_t)B * nc, a->loss, N, B, nc, s);
+    }
+    if (pl.train) {
+        // weight gradients dZ^T . (layer input) straight into G, bias gradients as row sums;
+        // dZ of the layer below through the weights, times ReLU's derivative
+        gemm(nc, F2, B, dz3, nc, (int64_t)B * nc, 1, h2, F2, (int64_t)B * F2, 0,
+             G + dl::kLenetFc3W, F2, ldg, dl::EPI_NONE, nullptr, nullptr, 0, G + fc3b, false);
+        gemm(B, F2, nc, dz3, nc, (int64_t)B * nc, 0, X + dl::kLenetFc3W, F2, ldx, 0, dz2, F2,
+             (int64_t)B * F2, dl::EPI_DRELU, nullptr, h2, F2, nullptr, false);
+        gemm(F2, F1, B, dz2, F2, (int64_t)B * F2, 1, h1, F1, (int64_t)B * F1, 0,
+             G + dl::kLenetFc2W, F1, ldg, dl::EPI_NONE, nullptr, nullptr, 0,
+             G + dl::kLenetFc2B, false);
+        gemm(B, F1, F2, dz2, F2, (int64_t)B * F2, 0, X + dl::kLenetFc2W, F1, ldx, 0, dz1, F1,
+             (int64_t)B * F1, dl::EPI_DRELU, nullptr, h1, F1, nullptr, false);
+        gemm(F1, P2, B, dz1, F1, (int64_t)B * F1, 1, pool2, P2, (int64_t)B * P2, 0,
+             G + dl::kLenetFc1W, P2, ldg, dl::EPI_NONE, nullptr, nullptr, 0,
+             G + dl::kLenetFc1B, false);
+        // the gradient entering the second pooling: dZ1 . fc1.weight
+        gemm(B, P2, F1, dz1, F1, (int64_t)B * F1, 0, X + dl::kLenetFc1W, P2, ldx, 0, da, P2,
+             (int64_t)B * P2, dl::EPI_NONE, nullptr, nullptr, 0, nullptr, false);
+        mark();
+        if (e == hipSuccess) e = dl::launch_lenet_conv_bwd(cv, pl.bwd_grid, s);
+        mark();
+        if (e == hipSuccess) e = dl::launch_lenet_conv_reduce(cv, N, s);
+    }
+    mark();   // after the last launch
+    return e == hipSuccess ? DL_OK : hip_fail(e, "lenet launch");
+}
+}  // namespace
+
+int dl_lenet_grad(const dl_lenet_args *a, void *workspace, size_t ws_bytes, dl_stream_t stream) {
+    return lenet_run(a, workspace, ws_bytes, static_cast<hipStream_t>(stream), nullptr, 0,
+                     nullptr);
+}
+
+int dl_lenet_grad_events(const dl_lenet_args *a, void *workspace, size_t ws_bytes,
+                         dl_stream_t stream, void *const *events, int32_t n_events,
+                         int32_t *n_launches) {
+    if (!events) return fail(DL_ERR_INVALID, "dl_lenet_grad_events: events is NULL");
+    return lenet_run(a, workspace, ws_bytes, static_cast<hipStream_t>(stream), events, n_events,
+                     n_launches);
+}
+
 int dl_stream_copy(const float *src, float *dst, int64_t n_floats, int32_t variant,
                    dl_stream_t stream) {
     g_err.clear();

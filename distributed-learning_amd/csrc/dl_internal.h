@@ -237,6 +237,29 @@ hipError_t launch_batch_gather(const BatchGatherPlan &p, int32_t *advance, hipSt
 // batch and, with `advance` (the cursor, writable), the one-thread launch that steps it
 hipError_t launch_image_batch(const ImageBatchPlan &p, int32_t *advance, hipStream_t s);
 
+// dl_lenet_grad's convolution kernels (lenet.hip) as launch.h shape_lenet shaped them.  The
+// workspace pointers are the regions of LenetWs (agent stride batch x the per-image size).
+struct LenetConvArgs {
+    const float *X;          // parameter rows; the 2872 convolution parameters lead each
+    int64_t ldx;
+    const float *data;       // [batch][3][32][32] per agent
+    int64_t s_data;
+    float *pool1;            // [batch][1176]: written by the forward with train, read by the backward
+    uint8_t *code1;          // [batch][1176] winner codes, likewise
+    float *pool2;            // [batch][400]: fc1's input, always written
+    uint8_t *code2;          // [batch][400]
+    const float *da;         // [batch][400]: d loss / d pool2 (backward)
+    float *part;             // [groups][2872] per agent: the backward's group partials
+    float *G;                // the reduce's destination
+    int64_t ldg;
+    int32_t batch, train;
+    int32_t passes, fwd_wpa, groups, bwd_wpa;
+};
+hipError_t launch_lenet_conv_fwd(const LenetConvArgs &p, int grid, hipStream_t s);
+hipError_t launch_lenet_conv_bwd(const LenetConvArgs &p, int grid, hipStream_t s);
+// G[a][j] = sum of agent a's group partials in group order, j < 2872
+hipError_t launch_lenet_conv_reduce(const LenetConvArgs &p, int n_agents, hipStream_t s);
+
 // sets dl_last_error()'s message (capi.hip) and returns code: for host-only entry points
 // defined outside capi.hip
 int fail_msg(int code, const char *msg);

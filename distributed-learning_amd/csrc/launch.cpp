@@ -745,4 +745,118 @@ int shape_image_batch(const dl_image_batch_args *a, int n_cus, ImageBatchPlan *o
     return DL_OK;
 }
 
+LenetWs lenet_workspace(int32_t n_agents, int32_t batch, int32_t num_classes) {
+    LenetWs w{};
+    if (n_agents < 1 || batch < 1 || num_classes < 1) return w;
+    const size_t nb = (size_t)n_agents * (size_t)batch;
+    const size_t groups = ((size_t)batch + kLenetGroup - 1) / kLenetGroup;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += align_up(bytes);
+        return at;
+    };
+    w.pool1 = take(nb * kLenetPool1 * 4);
+    w.code1 = take(nb * kLenetPool1);
+    w.pool2 = take(nb * kLenetPool2 * 4);
+    w.code2 = take(nb * kLenetPool2);
+    w.h1 = take(nb * kLenetFc1 * 4);
+    w.h2 = take(nb * kLenetFc2 * 4);
+    w.z = take(nb * (size_t)num_classes * 4);
+    w.dz3 = take(nb * (size_t)num_classes * 4);
+    w.dz2 = take(nb * kLenetFc2 * 4);
+    w.dz1 = take(nb * kLenetFc1 * 4);
+    w.da = take(nb * kLenetPool2 * 4);
+    w.part = take((size_t)n_agents * groups * kLenetConvParams * 4);
+    w.total = off;
+    return w;
+}
+
+int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_bytes,
+                LenetPlan *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_lenet_grad: args is NULL");
+    const int64_t N = a->n_agents, B = a->batch, nc = a->num_classes;
+    if (!a->X || !a->data) return fail(err, DL_ERR_INVALID, "dl_lenet_grad: null X or data");
+    if (!a->G && !a->loss && !a->logits)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: no output (G, loss and logits all NULL)");
+    if ((a->G || a->loss) && !a->labels)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: G and loss need labels");
+    if (N < 1 || B < 1)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: n_agents and batch must be >= 1 (got "
+                                         "%d, %d)", a->n_agents, a->batch);
+    if (N > 65535)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: at most 65535 agents (got %d)",
+                    a->n_agents);
+    if (nc < 1)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: num_classes must be >= 1 (got %d)",
+                    a->num_classes);
+    if (nc > kLenetMaxClasses)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_lenet_grad: the cross-entropy head takes at most "
+                                             "%d classes (got %d)", kLenetMaxClasses,
+                    a->num_classes);
+    const int64_t P = lenet_param_count(a->num_classes);
+    if (!aligned16(a->X) || !aligned16(a->data) || (a->G && !aligned16(a->G)))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: X, data and G must be 16-byte aligned");
+    if (a->ldx < P || (a->ldx & 3))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: ldx must be a multiple of 4 >= %lld "
+                                         "parameters (got %lld)", (long long)P, (long long)a->ldx);
+    if (a->G && (a->ldg < P || (a->ldg & 3)))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: ldg must be a multiple of 4 >= %lld "
+                                         "parameters (got %lld)", (long long)P, (long long)a->ldg);
+    if (a->s_data != 0 && (a->s_data < B * kLenetImage || (a->s_data & 3)))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: s_data must be 0 (shared) or a multiple "
+                                         "of 4 >= batch * 3072 (got %lld)", (long long)a->s_data);
+    if (a->labels && a->s_labels != 0 && a->s_labels < B)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: s_labels must be 0 (shared) or >= batch "
+                                         "(got %lld)", (long long)a->s_labels);
+    if (a->logits && (a->ldz < nc || (N > 1 && a->s_logits < (B - 1) * a->ldz + nc)))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_grad: logits need ldz >= num_classes and "
+                                         "s_logits >= (batch - 1) * ldz + num_classes (got ldz "
+                                         "%lld, s_logits %lld)", (long long)a->ldz,
+                    (long long)a->s_logits);
+    const LenetWs w = lenet_workspace(a->n_agents, a->batch, a->num_classes);
+    if (!ws_holds(ws, ws_bytes, w.total))
+        return fail(err, DL_ERR_WORKSPACE, "dl_lenet_grad: needs a 16-byte aligned workspace of "
+                                           "%zu bytes (dl_lenet_workspace_bytes)", w.total);
+    // no output may share a byte with an input or another output
+    struct Span { const void *p; size_t n; };
+    const Span in[3] = {{a->X, (size_t)((N - 1) * a->ldx + P) * 4},
+                        {a->data, (size_t)((N - 1) * a->s_data + B * kLenetImage) * 4},
+                        {a->labels, a->labels ? (size_t)((N - 1) * a->s_labels + B) * 4 : 0}};
+    const Span o[4] = {{a->G, a->G ? (size_t)((N - 1) * a->ldg + P) * 4 : 0},
+                       {a->loss, a->loss ? (size_t)N * 4 : 0},
+                       {a->logits, a->logits ? (size_t)((N - 1) * a->s_logits + (B - 1) * a->ldz +
+                                                        nc) * 4 : 0},
+                       {ws, w.total}};
+    static const char *const in_name[3] = {"X", "data", "labels"};
+    static const char *const out_name[4] = {"G", "loss", "logits", "workspace"};
+    for (int i = 0; i < 4; ++i) {
+        if (!o[i].n) continue;
+        for (int j = 0; j < 3; ++j)
+            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_lenet_grad: %s overlaps %s", out_name[i],
+                            in_name[j]);
+        for (int j = i + 1; j < 4; ++j)
+            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_lenet_grad: %s overlaps %s", out_name[i],
+                            out_name[j]);
+    }
+    if (!out) return DL_OK;
+    LenetPlan &p = *out;
+    p.train = a->G ? 1 : 0;
+    p.head = (a->G || a->loss) ? (B <= 64 ? 1 : 2) : 0;
+    p.passes = (int32_t)((B + kLenetFwdImages - 1) / kLenetFwdImages);
+    p.groups = (int32_t)((B + kLenetGroup - 1) / kLenetGroup);
+    const int64_t want = ((int64_t)kLenetWgPerCu * (n_cus > 0 ? n_cus : 1) + N - 1) / N;
+    p.fwd_wpa = (int32_t)(want < p.passes ? want : p.passes);
+    p.bwd_wpa = (int32_t)(want < p.groups ? want : p.groups);
+    p.fwd_grid = (int32_t)(N * p.fwd_wpa);   // <= 65535 + 4 * n_cus
+    p.bwd_grid = (int32_t)(N * p.bwd_wpa);
+    // conv forward, fc1, fc2, [fc3 -> logits], [fc3 + head: 1 or 2], [5 GEMMs, dA, conv
+    // backward, reduce]
+    p.n_launches = 3 + (a->logits ? 1 : 0) + p.head + (p.train ? 8 : 0);
+    p.ws = w;
+    return DL_OK;
+}
+
 }  // namespace dl

@@ -253,4 +253,51 @@ struct ImageBatchPlan {
 // kImageWavesPerCu) waves.
 int shape_image_batch(const dl_image_batch_args *a, int n_cus, ImageBatchPlan *out, char *err);
 
+// dl_lenet_grad: LeNet's fixed geometry, the workspace regions and the grids of the two
+// convolution kernels (lenet.hip).
+constexpr int kLenetImage = 3 * 32 * 32;     // floats of one input image
+constexpr int kLenetPool1 = 6 * 14 * 14;     // relu(conv1) pooled: conv2's input
+constexpr int kLenetPool2 = 16 * 5 * 5;      // relu(conv2) pooled: fc1's input, index c*25 + y*5 + x
+constexpr int kLenetFc1 = 120, kLenetFc2 = 84;
+constexpr int kLenetMaxClasses = 64;         // the cross-entropy head's limit
+// element offsets of the parameter blocks in a row (Mixer flatten order)
+constexpr int kLenetConv1W = 0, kLenetConv1B = 450, kLenetConv2W = 456, kLenetConv2B = 2856;
+constexpr int kLenetFc1W = 2872, kLenetFc1B = 50872, kLenetFc2W = 50992, kLenetFc2B = 61072;
+constexpr int kLenetFc3W = 61156;
+constexpr int kLenetConvParams = kLenetFc1W;   // the 2872 convolution parameters lead the row
+constexpr int32_t lenet_param_count(int32_t nc) { return nc < 1 ? 0 : kLenetFc3W + 85 * nc; }
+constexpr int kLenetThreads = 256;
+constexpr int kLenetFwdImages = 2;   // images a forward workgroup holds in LDS per pass
+constexpr int kLenetGroup = 4;       // images of one backward group: fixed, it sets the sum order
+// Workgroups per compute unit the grids aim at.  Either kernel holds three a compute unit
+// (forward: 51.8 KB of LDS, 130 VGPRs; backward: 143 VGPRs); 4 was chosen because at 64 agents x
+// 64 images it gives every workgroup exactly two passes / one group (no uneven split); 3 was
+// not measured against it.  Any value gives the same bits.
+constexpr int kLenetWgPerCu = 4;
+constexpr int kLenetMaxLaunches = 16;
+// Byte offsets of the workspace regions, each [n_agents][batch][...] with agent stride batch x
+// the per-image size, 256-byte aligned: the pooled activations and their winner codes (one byte
+// per pooled output: 0-3 = the window's first maximum in row-major order, 4 = none positive),
+// the Linear layers' activations and gradients, the gradient entering the second pooling, and
+// the convolution gradients' group partials [n_agents][groups][2872].
+struct LenetWs {
+    size_t pool1, code1, pool2, code2, h1, h2, z, dz3, dz2, dz1, da, part, total;
+};
+LenetWs lenet_workspace(int32_t n_agents, int32_t batch, int32_t num_classes);
+struct LenetPlan {
+    int32_t train;                // G given: the backward runs
+    int32_t head;                 // 0: no loss (logits only), 1: fused into fc3's GEMM, 2: fc3 +
+                                  // the stand-alone head (batch > 64)
+    int32_t passes, fwd_wpa;      // forward: ceil(batch / kLenetFwdImages) passes per agent;
+                                  // workgroup w of an agent walks passes w, w + fwd_wpa, ...
+    int32_t groups, bwd_wpa;      // backward: ceil(batch / kLenetGroup) groups, walked likewise
+    int32_t fwd_grid, bwd_grid;   // n_agents * wpa workgroups of kLenetThreads
+    int32_t n_launches;
+    LenetWs ws;
+};
+// Checks a dl_lenet_grad call and shapes it.  Either kernel runs wpa = ceil(kLenetWgPerCu *
+// n_cus / n_agents) workgroups per agent, at least 1 and at most the agent's passes / groups.
+int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_bytes,
+                LenetPlan *out, char *err);
+
 }  // namespace dl

@@ -37,6 +37,8 @@
  *   dl_image_batch      <- transform_train / transform_test of Man_Colab.ipynb cell 16
  *                          (RandomCrop(32, padding=4), RandomHorizontalFlip, ToTensor, Normalize)
  *                          on every node's next uint8 mini-batch, draws supplied by the caller
+ *   dl_lenet_grad       <- every node's LeNet forward, CrossEntropyLoss and backward
+ *                          (Man_Colab.ipynb cell 19, model_name = 'lenet'), all agents per call
  *
  * Conventions
  *   - Every pointer argument is a DEVICE pointer owned by the caller; nothing is allocated inside.
@@ -795,6 +797,79 @@ typedef struct dl_image_batch_args {
     int32_t *labels; int64_t s_labels;          /* out nullable; needs targets */
 } dl_image_batch_args;
 int dl_image_batch(const dl_image_batch_args *args, dl_stream_t stream);
+
+/* Per-agent gradients of LeNet, the model Man_Colab.ipynb cell 19 trains (model_name = 'lenet'),
+ * for all agents in one call: forward, torch.nn.CrossEntropyLoss (mean over the batch) and
+ * backward, each agent on its own batch with its own row of parameters.
+ *     conv1 = Conv2d(3, 6, 5)   conv2 = Conv2d(6, 16, 5)
+ *     fc1 = Linear(400, 120)    fc2 = Linear(120, 84)    fc3 = Linear(84, num_classes)
+ *     x[B,3,32,32] -> relu(conv1) -> max_pool2d(2) -> relu(conv2) -> max_pool2d(2)
+ *                  -> view(B, 400) (index c*25 + y*5 + x) -> relu(fc1) -> relu(fc2) -> fc3
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   Parameter rows are in the Mixer flatten order (mixer.py:68-69), element offsets
+ *     conv1.weight [6,3,5,5] 0, conv1.bias 450, conv2.weight [16,6,5,5] 456, conv2.bias 2856,
+ *     fc1.weight [120,400] 2872, fc1.bias 50872, fc2.weight [84,120] 50992, fc2.bias 61072,
+ *     fc3.weight [nc,84] 61156, fc3.bias 61156 + 84 nc;  P = dl_lenet_param_count(nc) =
+ *     61156 + 85 nc.  G has the same order.
+ *   Max-pool backward sends a window's gradient to its first maximum in row-major window order
+ *     (torch's rule); ReLU's derivative at 0 is 0, so a window whose maximum is <= 0 passes none.
+ *   G == NULL: forward only (evaluation); it writes logits and / or loss, one of which must then
+ *     be given.  With G, loss and logits stay optional.
+ *   Launches.  One call queues a fixed sequence on the stream: the convolution forward (both
+ *     stages, ReLU and pooling fused, fp32 FMA), the three Linear layers as dl_bgemm's GEMMs
+ *     (bias + ReLU epilogues; with logits, fc3 once more with the plain bias epilogue into
+ *     logits), the cross-entropy head (fused into fc3's GEMM at batch <= 64, else fc3 +
+ *     dl_xent_grad's kernel), and with G the five backward GEMMs of the Linear layers (weight
+ *     gradients straight into G, bias gradients as row sums), the GEMM dZ1 W1 that gives the
+ *     gradient entering the second pooling, the convolution backward and its reduce.
+ *   Summation order (no float atomics; results do not depend on the grid, and agent a's outputs
+ *     are the same bits whether it runs alone or among n_agents):
+ *     - a convolution output starts from its bias and adds input channels, kernel rows and kernel
+ *       columns in that order, one fma each;
+ *     - the GEMMs are k-ordered fma chains (dl_bgemm); the loss is dl_bgemm's / dl_xent_grad's;
+ *     - the gradient entering the first pooling adds conv2's output channels in order and, per
+ *       channel, its pooled windows in row-major order;
+ *     - a convolution weight gradient adds, per image, the pooled windows in row-major order (one
+ *       fma each; only a window's winner carries a gradient), images in order inside a group of
+ *       4 consecutive images of the batch, and then the ceil(batch / 4) group sums in group
+ *       order; a convolution bias gradient likewise.
+ *   Gates, each refused with its own message before any device call: DL_ERR_INVALID for null
+ *     args, X or data; no output (G, loss and logits all NULL); labels NULL with G or loss;
+ *     n_agents or batch < 1, n_agents > 65535, num_classes < 1; X, data or G not 16-byte
+ *     aligned; ldx, ldg or s_data not a multiple of 4; ldx or ldg < P; s_data neither 0 (one batch
+ *     shared by all agents) nor >= batch * 3072; s_labels neither 0 nor >= batch; with logits,
+ *     ldz < num_classes or (n_agents > 1) s_logits < (batch - 1) ldz + num_classes; any output
+ *     (G, loss, logits, workspace) sharing a byte with an input (X, data, labels) or another
+ *     output -- exact extents: operands that touch do not overlap.  DL_ERR_UNSUPPORTED for
+ *     num_classes > 64 (the cross-entropy head's limit).  DL_ERR_WORKSPACE for a workspace that
+ *     is NULL, not 16-byte aligned or smaller than dl_lenet_workspace_bytes.
+ *   Columns [P, ldg) of G and [num_classes, ldz) of logits are never written.  Labels outside
+ *     [0, num_classes) give undefined loss and gradient values, never an out-of-bounds access.
+ *   X and data must be finite.  The backward multiplies a zero gradient (a window with no
+ *     winner, a gather slot out of reach) by a value it loads anyway -- a pixel, a pooled
+ *     activation, a conv2 weight, possibly at another position -- which is exact for finite
+ *     values; an Inf or NaN there would reach gradients that torch leaves finite.
+ *   Row-major operands only.  Stream-ordered, no allocation, no host synchronisation: capturable
+ *     in a hipGraph. */
+typedef struct dl_lenet_args {
+    int32_t n_agents, batch, num_classes;
+    const float *X; int64_t ldx;              /* [n_agents][ldx >= P] row-major parameter rows */
+    const float *data; int64_t s_data;        /* [batch][3][32][32] per agent; agent stride, 0 = shared */
+    const int32_t *labels; int64_t s_labels;  /* [batch]; 0 = shared; nullable iff G and loss are NULL */
+    float *G; int64_t ldg;                    /* nullable: d loss_a / d params_a, columns [P, ldg) never written */
+    float *loss;                              /* nullable [n_agents] */
+    float *logits; int64_t ldz, s_logits;     /* nullable [n_agents][batch][ldz >= num_classes] */
+} dl_lenet_args;
+int32_t dl_lenet_param_count(int32_t num_classes);   /* 0 when num_classes < 1 */
+size_t dl_lenet_workspace_bytes(int32_t n_agents, int32_t batch, int32_t num_classes);
+int dl_lenet_grad(const dl_lenet_args *args, void *workspace, size_t ws_bytes, dl_stream_t stream);
+/* The same call with a HIP event recorded on the stream before each of its launches and one
+ * after the last (a measurement aid: the time between consecutive events is one launch's).
+ * events: host array of n_events hipEvent_t created by the caller; *n_launches (nullable)
+ * receives the launches queued.  Fewer events than launches + 1: DL_ERR_INVALID, nothing runs. */
+int dl_lenet_grad_events(const dl_lenet_args *args, void *workspace, size_t ws_bytes,
+                         dl_stream_t stream, void *const *events, int32_t n_events,
+                         int32_t *n_launches);
 
 #ifdef __cplusplus
 }
