@@ -142,7 +142,18 @@ class DlLenetArgs(ctypes.Structure):
                 ("ldz", _i64), ("s_logits", _i64)]
 
 
-EPI = {"none": 0, "bias": 1, "bias_relu": 2, "bias_tanh": 3, "bias_elu": 4, "drelu": 5,
+class DlLenetEvalArgs(ctypes.Structure):
+    _fields_ = [("n_agents", _i32), ("rows", _i32), ("num_classes", _i32), ("X", _vp),
+                ("ldx", _i64), ("data", _vp), ("s_data", _i64), ("labels", _vp),
+                ("s_labels", _i64), ("loss", _vp), ("correct", _vp), ("logits", _vp),
+                ("ldz", _i64), ("s_logits", _i64), ("row_splits", _i32)]
+
+
+class DlLenetEvalPlan(ctypes.Structure):
+    _fields_ = [("blocks", _i32), ("row_splits", _i32), ("grid", _i32), ("lds_bytes", _i32)]
+
+
+EPI ={"none": 0, "bias": 1, "bias_relu": 2, "bias_tanh": 3, "bias_elu": 4, "drelu": 5,
        "dtanh": 6, "delu": 7, "bias_xent": 8}
 
 # exported symbol -> (restype, argtypes); tests check every one is exported
@@ -195,6 +206,10 @@ SIGNATURES = {
     "dl_lenet_grad": (_i32, [ctypes.POINTER(DlLenetArgs), _vp, _sz, _vp]),
     "dl_lenet_grad_events": (_i32, [ctypes.POINTER(DlLenetArgs), _vp, _sz, _vp,
                                     ctypes.POINTER(_vp), _i32, ctypes.POINTER(_i32)]),
+    "dl_lenet_eval_workspace_bytes": (_sz, [_i32, _i32]),
+    "dl_lenet_eval_plan_query": (_i32, [ctypes.POINTER(DlLenetEvalArgs),
+                                        ctypes.POINTER(DlLenetEvalPlan)]),
+    "dl_lenet_eval": (_i32, [ctypes.POINTER(DlLenetEvalArgs), _vp, _sz, _vp]),
     "dl_bgemm": (_i32, [ctypes.POINTER(DlBgemmArgs), _vp]),
     "dl_xent_grad": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),
     "dl_perron_workspace_bytes": (_sz, [_i32, _i32, _i64]),

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "dl_internal.h"
+#include "lenet_ops.h"   // xent_row: shared with lenet_eval.hip
 
 namespace dl {
 namespace {
@@ -66,21 +67,6 @@ __device__ __forceinline__ float act_grad(int epi, float h) {
         case EPI_DELU: return h > 0.f ? 1.f : h + 1.f;
         default: return 1.f;
     }
-}
-
-// softmax cross-entropy of one logits row held one class per lane (classes <= 64):
-// writes dZ = (softmax - onehot) / rows and returns the row's loss / rows (meaningful on all
-// lanes).  torch.nn.CrossEntropyLoss, mean reduction.
-__device__ __forceinline__ float xent_row(float v, int lane, int classes, int label, int rows,
-                                          float *dz_row) {
-    float mx = lane < classes ? v : -INFINITY;
-    for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-    const float e = lane < classes ? expf(v - mx) : 0.f;
-    float sum = e;
-    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
-    if (lane < classes) dz_row[lane] = (e / sum - (lane == label ? 1.f : 0.f)) / (float)rows;
-    const float zl = __shfl(v, label);
-    return (logf(sum) + mx - zl) / (float)rows;
 }
 
 // Block tile BM x BN = (16 TM WM) x (16 TN WN): the 4 waves form a WM x WN grid and each owns

@@ -997,6 +997,38 @@ int dl_lenet_grad_events(const dl_lenet_args *a, void *workspace, size_t ws_byte
                      n_launches);
 }
 
+size_t dl_lenet_eval_workspace_bytes(int32_t n_agents, int32_t rows) {
+    return dl::lenet_eval_workspace(n_agents, rows).total;
+}
+
+int dl_lenet_eval_plan_query(const dl_lenet_eval_args *a, dl_lenet_eval_plan *plan) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    int rc = dl::shape_lenet_eval(a, device_cus(), nullptr, 0, false, plan, err);
+    if (rc) return status(rc, err);
+    if (!plan) return fail(DL_ERR_INVALID, "dl_lenet_eval_plan_query: plan is NULL");
+    return DL_OK;
+}
+
+int dl_lenet_eval(const dl_lenet_eval_args *a, void *workspace, size_t ws_bytes,
+                  dl_stream_t stream) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    dl_lenet_eval_plan pl;
+    int rc = dl::shape_lenet_eval(a, device_cus(), workspace, ws_bytes, true, &pl, err);
+    if (rc) return status(rc, err);
+    const dl::LenetEvalWs w = dl::lenet_eval_workspace(a->n_agents, a->rows);
+    char *ws = static_cast<char *>(workspace);
+    const dl::LenetEvalArgs p{a->X, a->ldx, a->data, a->s_data, a->labels, a->s_labels,
+                              reinterpret_cast<float *>(ws + w.part),
+                              reinterpret_cast<int32_t *>(ws + w.hit), a->logits, a->ldz,
+                              a->s_logits, a->n_agents, a->rows, pl.blocks, pl.row_splits,
+                              a->num_classes};
+    hipError_t e = dl::launch_lenet_eval(p, pl.lds_bytes, a->loss, a->correct,
+                                         static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DL_OK : hip_fail(e, "lenet_eval launch");
+}
+
 int dl_stream_copy(const float *src, float *dst, int64_t n_floats, int32_t variant,
                    dl_stream_t stream) {
     g_err.clear();

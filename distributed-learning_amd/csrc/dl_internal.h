@@ -228,6 +228,10 @@ struct MlpEvalArgs {
 // block-order reduce after it
 hipError_t launch_mlp_eval(const MlpEvalArgs &p, int n_agents, float *loss, int32_t *correct,
                            hipStream_t s);
+// that reduce (also dl_lenet_eval's): loss[a] = (float)((sum_b (double)part[a][b]) * 64 / rows),
+// correct[a] = sum_b hit[a][b], both in block order; loss or correct may be NULL
+hipError_t launch_eval_reduce(const float *part, const int32_t *hit, int n_agents, int blocks,
+                              int rows, float *loss, int32_t *correct, hipStream_t s);
 
 // dl_batch_gather's launches (batch_gather.hip) as launch.h shape_batch_gather shaped them: the
 // gather and, with `advance` (the cursor, writable), the one-thread launch that steps it
@@ -259,6 +263,25 @@ hipError_t launch_lenet_conv_fwd(const LenetConvArgs &p, int grid, hipStream_t s
 hipError_t launch_lenet_conv_bwd(const LenetConvArgs &p, int grid, hipStream_t s);
 // G[a][j] = sum of agent a's group partials in group order, j < 2872
 hipError_t launch_lenet_conv_reduce(const LenetConvArgs &p, int n_agents, hipStream_t s);
+
+// dl_lenet_eval's kernel parameter (lenet_eval.hip), after launch.h shape_lenet_eval
+struct LenetEvalArgs {
+    const float *X;          // parameter rows
+    int64_t ldx;
+    const float *data;       // [rows][3][32][32] per agent
+    int64_t s_data;
+    const int32_t *labels;   // nullable with loss == correct == NULL (logits only)
+    int64_t s_lab;
+    float *part;             // [n_agents][blocks] per-block loss parts (workspace)
+    int32_t *hit;            // [n_agents][blocks] per-block correct counts (workspace)
+    float *logits;           // nullable
+    int64_t ldz, s_logits;
+    int32_t n_agents, rows, blocks, row_splits, nc;
+};
+// the evaluation launch on n_agents * row_splits workgroups with lds_bytes of LDS and, with loss
+// or correct, the block-order reduce after it
+hipError_t launch_lenet_eval(const LenetEvalArgs &p, int lds_bytes, float *loss, int32_t *correct,
+                             hipStream_t s);
 
 // sets dl_last_error()'s message (capi.hip) and returns code: for host-only entry points
 // defined outside capi.hip

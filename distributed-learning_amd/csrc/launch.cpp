@@ -859,4 +859,97 @@ int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_byt
     return DL_OK;
 }
 
+LenetEvalWs lenet_eval_workspace(int32_t n_agents, int32_t rows) {
+    LenetEvalWs w{};
+    if (n_agents < 1 || rows < 1) return w;
+    w.hit = eval_part_bytes(n_agents, rows);
+    w.total = 2 * w.hit;
+    return w;
+}
+
+int shape_lenet_eval(const dl_lenet_eval_args *a, int n_cus, const void *ws, size_t ws_bytes,
+                     bool check_ws, dl_lenet_eval_plan *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_lenet_eval: args is NULL");
+    const int64_t N = a->n_agents, R = a->rows, nc = a->num_classes;
+    if (!a->X || !a->data) return fail(err, DL_ERR_INVALID, "dl_lenet_eval: null X or data");
+    if (!a->loss && !a->correct && !a->logits)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: no output (loss, correct and logits all "
+                                         "NULL)");
+    if ((a->loss || a->correct) && !a->labels)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: loss and correct need labels");
+    if (N < 1) return fail(err, DL_ERR_INVALID, "dl_lenet_eval: n_agents must be >= 1 (got %d)",
+                           a->n_agents);
+    if (N > 65535)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: at most 65535 agents (got %d)",
+                    a->n_agents);
+    if (R < 1) return fail(err, DL_ERR_INVALID, "dl_lenet_eval: rows must be >= 1 (got %d)",
+                           a->rows);
+    if (nc < 1)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: num_classes must be >= 1 (got %d)",
+                    a->num_classes);
+    if (nc > kLenetMaxClasses)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_lenet_eval: the cross-entropy head takes at most "
+                                             "%d classes (got %d)", kLenetMaxClasses,
+                    a->num_classes);
+    const int64_t P = lenet_param_count(a->num_classes);
+    if (!aligned16(a->X) || !aligned16(a->data))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: X and data must be 16-byte aligned");
+    if (a->ldx < P || (a->ldx & 3))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: ldx must be a multiple of 4 >= %lld "
+                                         "parameters (got %lld)", (long long)P, (long long)a->ldx);
+    if (a->s_data != 0 && (a->s_data < R * kLenetImage || (a->s_data & 3)))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: s_data must be 0 (shared) or a multiple "
+                                         "of 4 >= rows * 3072 (got %lld)", (long long)a->s_data);
+    if (a->labels && a->s_labels != 0 && a->s_labels < R)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: s_labels must be 0 (shared) or >= rows "
+                                         "(got %lld)", (long long)a->s_labels);
+    if (a->logits && (a->ldz < nc || (N > 1 && a->s_logits < (R - 1) * a->ldz + nc)))
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: logits need ldz >= num_classes and "
+                                         "s_logits >= (rows - 1) * ldz + num_classes (got ldz "
+                                         "%lld, s_logits %lld)", (long long)a->ldz,
+                    (long long)a->s_logits);
+    if (a->row_splits < 0)
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: row_splits must be >= 0 (got %d)",
+                    a->row_splits);
+    const LenetEvalWs w = lenet_eval_workspace(a->n_agents, a->rows);
+    if (check_ws && !ws_holds(ws, ws_bytes, w.total))
+        return fail(err, DL_ERR_WORKSPACE, "dl_lenet_eval: needs a 16-byte aligned workspace of "
+                                           "%zu bytes (dl_lenet_eval_workspace_bytes)", w.total);
+    // no output may share a byte with an input or another output
+    struct Span { const void *p; size_t n; };
+    const Span in[3] = {{a->X, (size_t)((N - 1) * a->ldx + P) * 4},
+                        {a->data, (size_t)((N - 1) * a->s_data + R * kLenetImage) * 4},
+                        {a->labels, a->labels ? (size_t)((N - 1) * a->s_labels + R) * 4 : 0}};
+    const Span o[4] = {{a->loss, a->loss ? (size_t)N * 4 : 0},
+                       {a->correct, a->correct ? (size_t)N * 4 : 0},
+                       {a->logits, a->logits ? (size_t)((N - 1) * a->s_logits + (R - 1) * a->ldz +
+                                                        nc) * 4 : 0},
+                       {ws, check_ws ? w.total : 0}};
+    static const char *const in_name[3] = {"X", "data", "labels"};
+    static const char *const out_name[4] = {"loss", "correct", "logits", "workspace"};
+    for (int i = 0; i < 4; ++i) {
+        if (!o[i].n) continue;
+        for (int j = 0; j < 3; ++j)
+            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_lenet_eval: %s overlaps %s", out_name[i],
+                            in_name[j]);
+        for (int j = i + 1; j < 4; ++j)
+            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_lenet_eval: %s overlaps %s", out_name[i],
+                            out_name[j]);
+    }
+    const int32_t blocks = eval_blocks(a->rows);
+    int64_t rs = a->row_splits > 0
+                     ? a->row_splits
+                     : ((int64_t)kLenetEvalWgPerCu * (n_cus > 0 ? n_cus : 1) + N - 1) / N;
+    if (rs > blocks) rs = blocks;
+    if (rs < 1) rs = 1;
+    if (N * rs > 0x7fffffff)   // only a hint can ask for this: the chosen rs is <= 2 n_cus
+        return fail(err, DL_ERR_INVALID, "dl_lenet_eval: grid too large (n_agents * row_splits "
+                                         "must be < 2^31)");
+    if (out)
+        *out = dl_lenet_eval_plan{blocks, (int32_t)rs, (int32_t)(N * rs), kLenetEvalLdsBytes};
+    return DL_OK;
+}
+
 }  // namespace dl

@@ -300,4 +300,20 @@ struct LenetPlan {
 int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_bytes,
                 LenetPlan *out, char *err);
 
+// dl_lenet_eval: blocks of kEvalBlockRows rows as dl_mlp_eval's, the LDS of one workgroup
+// (lenet_eval.hip asserts it: two workgroups a compute unit), and the workspace: [n_agents]
+// [blocks] float loss parts at `part`, then as many int32 correct counts at `hit`.
+constexpr int kLenetEvalLdsBytes = 72128;
+constexpr int kLenetEvalWgPerCu = 2;
+struct LenetEvalWs {
+    size_t part, hit, total;
+};
+LenetEvalWs lenet_eval_workspace(int32_t n_agents, int32_t rows);
+// Checks a dl_lenet_eval call and shapes its grid: blocks = ceil(rows / 64); row_splits =
+// ceil(kLenetEvalWgPerCu * n_cus / n_agents), at least 1 and at most `blocks`; the caller's hint
+// (args.row_splits > 0) instead, clamped to [1, blocks].  check_ws: the workspace too
+// (dl_lenet_eval; the plan query has none).
+int shape_lenet_eval(const dl_lenet_eval_args *a, int n_cus, const void *ws, size_t ws_bytes,
+                     bool check_ws, dl_lenet_eval_plan *out, char *err);
+
 }  // namespace dl

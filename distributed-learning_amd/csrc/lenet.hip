@@ -23,57 +23,14 @@
 // kernel columns of the 2872 gradients and keeps them in registers over a group of kLenetGroup
 // images; group sums go to the workspace and lenet_conv_reduce_kernel adds them in group order.
 #include "dl_internal.h"
+#include "lenet_ops.h"   // pool_relu, conv_window: shared with lenet_eval.hip
 
 namespace dl {
 namespace {
 
 constexpr int FI = kLenetFwdImages;
 constexpr int NT = kLenetThreads;
-constexpr int kNone = 4;   // winner code: no positive value in the window
-
-// winner of a 2 x 2 window in row-major order (first maximum, as torch's max_pool2d) after
-// ReLU: the value kept and its code
-__device__ __forceinline__ float pool_relu(float a00, float a01, float a10, float a11, int &code) {
-    float m = a00;
-    code = 0;
-    if (a01 > m) { m = a01; code = 1; }
-    if (a10 > m) { m = a10; code = 2; }
-    if (a11 > m) { m = a11; code = 3; }
-    if (!(m > 0.f)) { m = 0.f; code = kNone; }
-    return m;
-}
-
-// The four convolution outputs (5 x 5 kernel) of one pooling window over CI input planes of
-// `plane` floats and `row` floats per row; ip: the window's top-left input, 8-byte aligned;
-// wp: the output channel's [CI][25] weights.  Sum order: bias, then ci, ky, kx.
-template <int CI>
-__device__ __forceinline__ float conv_window(const float *ip, int plane, int row, const float *wp,
-                                             float bias, int &code) {
-    float a00 = bias, a01 = bias, a10 = bias, a11 = bias;
-#pragma unroll 1
-    for (int ci = 0; ci < CI; ++ci) {
-        float pt[6][6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float2 v = *reinterpret_cast<const float2 *>(ip + ci * plane + r * row + 2 * c);
-                pt[r][2 * c] = v.x;
-                pt[r][2 * c + 1] = v.y;
-            }
-#pragma unroll
-        for (int ky = 0; ky < 5; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 5; ++kx) {
-                const float w = wp[ci * 25 + ky * 5 + kx];
-                a00 = fmaf(w, pt[ky][kx], a00);
-                a01 = fmaf(w, pt[ky][kx + 1], a01);
-                a10 = fmaf(w, pt[ky + 1][kx], a10);
-                a11 = fmaf(w, pt[ky + 1][kx + 1], a11);
-            }
-    }
-    return pool_relu(a00, a01, a10, a11, code);
-}
+constexpr int kNone = kPoolNone;   // winner code: no positive value in the window
 
 __global__ __launch_bounds__(NT) void lenet_conv_fwd_kernel(const LenetConvArgs a) {
     __shared__ __attribute__((aligned(16))) float s_w[kLenetConvParams];

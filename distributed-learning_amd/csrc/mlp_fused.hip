@@ -1879,8 +1879,13 @@ hipError_t launch_mlp_eval(const MlpEvalArgs &p, int n_agents, float *loss, int3
                   : (head ? pick(std::false_type{}, std::true_type{})
                           : pick(std::false_type{}, std::false_type{}));
     if (e != hipSuccess || !head) return e;
+    return launch_eval_reduce(p.part, p.hit, n_agents, p.blocks, p.rows, loss, correct, s);
+}
+
+hipError_t launch_eval_reduce(const float *part, const int32_t *hit, int n_agents, int blocks,
+                              int rows, float *loss, int32_t *correct, hipStream_t s) {
     hipLaunchKernelGGL(mlp_eval_reduce_kernel, dim3((unsigned)((n_agents + 255) / 256)), dim3(256),
-                       0, s, p.part, p.hit, n_agents, p.blocks, p.rows, loss, correct);
+                       0, s, part, hit, n_agents, blocks, rows, loss, correct);
     return hipGetLastError();
 }
 

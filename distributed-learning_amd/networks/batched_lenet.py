@@ -21,8 +21,9 @@ IMAGE = 3 * 32 * 32
 class BatchedLeNet:
     path = "layers"   # what MLPConsensusSGD asks of a model that reads X row-major
 
-    def __init__(self, n_agents, batch, num_classes=10, device="cuda"):
+    def __init__(self, n_agents, batch, num_classes=10, device="cuda", fused_eval=False):
         self.N, self.B = int(n_agents), int(batch)
+        self.fused_eval = bool(fused_eval)   # evaluate's default path: one dl_lenet_eval call
         self.din, self.dout = IMAGE, int(num_classes)
         if not 1 <= self.dout <= 64:
             raise ValueError("the cross-entropy head supports 1 to 64 classes")
@@ -38,6 +39,7 @@ class BatchedLeNet:
         # holds its address.  evaluate has its own (it grows with the chunk), as BatchedANN's.
         self.ws = None
         self.eval_ws = self.eval_out = self.eval_logits = self.eval_acc = None
+        self.fused_ws = self.fused_out = None   # dl_lenet_eval's workspace and (loss, correct)
 
     def _workspace(self, rows, evaluate=False):
         need = _lib.load().dl_lenet_workspace_bytes(self.N, int(rows), self.dout)
@@ -78,7 +80,7 @@ class BatchedLeNet:
                                              _lib.stream_handle(self.device)), "dl_lenet_grad")
         return self.loss
 
-    def evaluate(self, X, data, labels, logits=None, row_splits=0, chunk=512):
+    def evaluate(self, X, data, labels, logits=None, row_splits=0, chunk=512, fused=None):
         """Every agent's model on a test set, forward only: returns (loss[N] fp32 mean
         cross-entropy, correct[N] int32 rows whose logit argmax is the label), the per-node
         statistics of the reference's MasterNode (Man_Colab.ipynb cells 21-23).
@@ -88,8 +90,8 @@ class BatchedLeNet:
         optional fp32 [N, R, num_classes] output with a contiguous last dimension.  The rows go
         through the forward-only ``dl_lenet_grad`` in chunks of ``chunk``; the loss and the
         argmax come from each chunk's logits with torch ops, summed in fp64.  ``row_splits`` is
-        accepted for ``BatchedANN``'s signature and ignored.  The returned tensors are this
-        object's, overwritten by the next call.
+        accepted for ``BatchedANN``'s signature and ignored on this path.  The returned tensors
+        are this object's, overwritten by the next call.
 
         Stream-ordered with no host synchronisation.  The workspace (separate from
         ``gradients``'), the logits chunk, the accumulators and the outputs are this object's and
@@ -97,7 +99,15 @@ class BatchedLeNet:
         the torch ops on each chunk's logits allocate their temporaries from torch's caching
         allocator on every call, which a ``torch.cuda.graph`` capture serves from the graph's
         pool.  A captured ``evaluate`` holds the addresses of its call: capture it after the
-        largest chunk it will be asked for."""
+        largest chunk it will be asked for.
+
+        fused (None: the constructor's ``fused_eval``) true: one ``dl_lenet_eval`` call for the
+        whole test set instead -- the forward and the head in one kernel with the activations in
+        LDS, then a block-order reduce (include/dlamd.h states the sum order).  ``row_splits`` is
+        forwarded (0 = chosen; any value gives the same bits) and ``chunk`` ignored.  Once its
+        buffers exist -- the outputs and a workspace of two numbers per 64 rows, allocated on
+        first use and regrown only for more rows -- the call runs no torch op and allocates
+        nothing: a capture is two kernels."""
         N, dout = self.N, self.dout
         per_agent = data.dim() in (3, 5)
         if data.dim() not in (2, 3, 4, 5) or data.dtype != torch.float32 or \
@@ -122,6 +132,8 @@ class BatchedLeNet:
             raise ValueError(f"logits must be fp32 [{N}, {R}, {dout}] with a contiguous last "
                              "dimension and non-overlapping rows")
         self._check_rows(X)
+        if self.fused_eval if fused is None else fused:
+            return self._evaluate_fused(X, data, s_data, R, labels, logits, row_splits)
         chunk = min(chunk, R)
         if logits is None:
             if self.eval_logits is None or self.eval_logits.shape[1] < chunk:
@@ -160,6 +172,28 @@ class BatchedLeNet:
         loss, correct = self.eval_out
         loss.copy_(lsum / R)
         correct.copy_(hits)
+        return loss, correct
+
+    def _evaluate_fused(self, X, data, s_data, R, labels, logits, row_splits):
+        lib = _lib.load()
+        if labels is not None and labels.stride(-1) != 1:
+            raise ValueError("labels must have a contiguous last dimension")
+        if self.fused_ws is None or self.fused_ws[1] < R:
+            need = lib.dl_lenet_eval_workspace_bytes(self.N, R)
+            self.fused_ws = (torch.empty(need // 4, dtype=torch.float32, device=self.device), R)
+        if self.fused_out is None:
+            self.fused_out = (torch.empty(self.N, dtype=torch.float32, device=self.device),
+                              torch.empty(self.N, dtype=torch.int32, device=self.device))
+        loss, correct = self.fused_out if labels is not None else (None, None)
+        ws = self.fused_ws[0]
+        args = _lib.DlLenetEvalArgs(
+            self.N, R, self.dout, _lib.ptr(X), X.stride(0), _lib.ptr(data), s_data,
+            _lib.ptr(labels), labels.stride(0) if labels is not None and labels.dim() == 2 else 0,
+            _lib.ptr(loss), _lib.ptr(correct), _lib.ptr(logits),
+            logits.stride(1) if logits is not None else 0,
+            logits.stride(0) if logits is not None else 0, int(row_splits))
+        _lib.check(lib.dl_lenet_eval(ctypes.byref(args), _lib.ptr(ws), ws.numel() * 4,
+                                     _lib.stream_handle(self.device)), "dl_lenet_eval")
         return loss, correct
 
     def flops_per_step(self):

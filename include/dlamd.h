@@ -39,6 +39,8 @@
  *                          on every node's next uint8 mini-batch, draws supplied by the caller
  *   dl_lenet_grad       <- every node's LeNet forward, CrossEntropyLoss and backward
  *                          (Man_Colab.ipynb cell 19, model_name = 'lenet'), all agents per call
+ *   dl_lenet_eval       <- MasterNode's per-node test statistics through LeNet, Man_Colab.ipynb
+ *                          cells 21-23
  *
  * Conventions
  *   - Every pointer argument is a DEVICE pointer owned by the caller; nothing is allocated inside.
@@ -870,6 +872,75 @@ int dl_lenet_grad(const dl_lenet_args *args, void *workspace, size_t ws_bytes, d
 int dl_lenet_grad_events(const dl_lenet_args *args, void *workspace, size_t ws_bytes,
                          dl_stream_t stream, void *const *events, int32_t n_events,
                          int32_t *n_launches);
+
+/* Per-agent evaluation of LeNet on a test set, forward only, in one launch plus a tiny reduce:
+ * every agent's mean cross-entropy, its number of correctly classified rows and, optionally, its
+ * logits -- the per-node `accuracy ..., loss ...` that the reference's MasterNode prints every
+ * stat_step from one shared test_loader (Man_Colab.ipynb cells 21-23) with model_name = 'lenet'.
+ * dl_mlp_eval's counterpart for dl_lenet_grad's model: X, data, labels and logits as in
+ * dl_lenet_args (row-major parameter rows in the Mixer flatten order).  Activations never go to
+ * HBM: they stay in LDS.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   Limits, each refused with its own message before any device call: DL_ERR_INVALID for null
+ *     args, X or data; no output (loss, correct and logits all NULL); labels NULL with loss or
+ *     correct; n_agents < 1 or > 65535; rows < 1; num_classes < 1; X or data not 16-byte aligned;
+ *     ldx not a multiple of 4 or < P = dl_lenet_param_count(num_classes); s_data neither 0 (one
+ *     test set shared by all agents, the reference's case) nor a multiple of 4 >= rows * 3072;
+ *     s_labels neither 0 nor >= rows; with logits, ldz < num_classes or (n_agents > 1) s_logits <
+ *     (rows - 1) ldz + num_classes; row_splits < 0, or a hint so large that n_agents * row_splits
+ *     reaches 2^31; any output (loss, correct, logits, workspace) sharing a byte with an input (X,
+ *     data, labels) or another output -- exact extents: operands that touch do not overlap.
+ *     DL_ERR_UNSUPPORTED for num_classes > 64 (the cross-entropy head's limit).
+ *     DL_ERR_WORKSPACE for a workspace that is NULL, not 16-byte aligned or smaller than
+ *     dl_lenet_eval_workspace_bytes.  rows * 3072 * 4 may pass 4 GiB: row and agent bases are
+ *     64-bit.
+ *   Blocks.  An agent's rows are cut into blocks of 64; one workgroup per (agent, row split)
+ *     walks blocks split, split + row_splits, ...
+ *   Logits are, bit for bit, what the forward-only dl_lenet_grad writes for the same inputs: a
+ *     convolution output starts from its bias and adds input channels, kernel rows and kernel
+ *     columns in that order, one fma each; each Linear output is a k-ordered fp32 fma chain from
+ *     0 over the whole K (v_mfma_f32_16x16x4_f32, as dl_bgemm), then + bias, then ReLU.
+ *   Block sums.  Block b leaves in the workspace part[a][b] = the sum over its valid rows of
+ *     term_r / 64, term_r = logf(sum_c expf(z_r[c] - max)) + max - z_r[label_r] computed as
+ *     dl_bgemm's cross-entropy head does (the same butterflies over 64 lanes), summed in that
+ *     head's order: wave w of 4 adds rows w, w + 4, ... in increasing order, then (l0 + l1) +
+ *     (l2 + l3).  A full block's part is therefore, bit for bit, the loss dl_lenet_grad returns
+ *     for those 64 rows as a batch.
+ *   Hits.  hit[a][b] = the block's rows whose logit argmax is the label (first maximum on ties,
+ *     as torch.argmax; a row with a NaN logit counts as wrong).
+ *   Reduce.  A second, tiny launch sums in block order, no float atomics:
+ *         loss[a]    = (float)((sum_b (double)part[a][b]) * 64 / rows)
+ *         correct[a] = sum_b hit[a][b]
+ *     so the results do not depend on row_splits, the grid or n_agents.
+ *   Containment.  Rows past the end of a short last block are masked: nothing is read past data
+ *     or labels and their logits are not stored.  Labels outside [0, num_classes) give undefined
+ *     loss / correct values, never an out-of-bounds access.  Columns [num_classes, ldz) of logits
+ *     are never written and columns [P, ldx) of X never read.
+ *   Workspace: dl_lenet_eval_workspace_bytes(n_agents, rows) bytes, 16-byte aligned; it holds
+ *     only part and hit ([n_agents][ceil(rows / 64)] floats and as many int32, each rounded up to
+ *     256 bytes).
+ *   Stream-ordered, no allocation, no host synchronisation: capturable in a hipGraph, where a
+ *     call with loss or correct is a linear graph of two kernels (logits alone: one).
+ * dl_lenet_eval_plan_query: DL_OK and the grid the call would run (blocks = ceil(rows / 64);
+ * row_splits chosen so that n_agents * row_splits workgroups cover the compute units at the
+ * kernel's two workgroups per unit, at most blocks; a row_splits hint > 0 instead, clamped to
+ * [1, blocks]; lds_bytes = what the kernel declares), or the refusal, without touching the
+ * device (the workspace is not part of the query). */
+typedef struct dl_lenet_eval_args {
+    int32_t n_agents, rows, num_classes;
+    const float *X; int64_t ldx;              /* as dl_lenet_args: row-major parameter rows */
+    const float *data; int64_t s_data;        /* [rows][3][32][32]; agent stride, 0 = shared */
+    const int32_t *labels; int64_t s_labels;  /* [rows]; 0 = shared; nullable iff loss and correct are NULL */
+    float *loss;        /* nullable [n_agents]: mean cross-entropy over the rows */
+    int32_t *correct;   /* nullable [n_agents] */
+    float *logits; int64_t ldz, s_logits;     /* nullable [n_agents][rows][ldz >= num_classes] */
+    int32_t row_splits; /* 0 = choose; a hint: any value gives the same bits */
+} dl_lenet_eval_args;
+typedef struct dl_lenet_eval_plan { int32_t blocks, row_splits, grid, lds_bytes; } dl_lenet_eval_plan;
+size_t dl_lenet_eval_workspace_bytes(int32_t n_agents, int32_t rows);
+int dl_lenet_eval_plan_query(const dl_lenet_eval_args *args, dl_lenet_eval_plan *plan);
+int dl_lenet_eval(const dl_lenet_eval_args *args, void *workspace, size_t ws_bytes,
+                  dl_stream_t stream);
 
 #ifdef __cplusplus
 }
