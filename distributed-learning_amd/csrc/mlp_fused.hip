@@ -23,8 +23,13 @@
 //     ds_read_b64 pairing of k that is conflict-free measured no faster: not the bottleneck)
 //   [k][col] images read by 16 cols x 4 k   -> stride = 16 (mod 32) floats (176): conflict-free
 //   [k][col] images read by 32 cols x 2 k (32x32x2) -> stride = 32 (mod 64) floats (288)
-// f32 MFMA (16x16x4) products are exact fp32 fma chains; summation order differs from
-// autograd's BLAS, so parity is a tolerance (tests/test_batched_ann_gpu.py).
+// Arithmetic: layer 1, the hidden forward GEMMs, dZ2, dZ1 and dW1 run as bf16x6 (below), the
+// rest as fp32 fma chains on the f32 MFMA.  Asserted (tests/test_mlp_x6_gpu.py): per agent and
+// parameter block, and for dl_mlp_eval's logits, the error against float64 is at most 3 x the
+// layered path's (dl_bgemm, itself pinned bit for bit to an fma-chain oracle) or 3 x 2^-23 of
+// the block's largest entry -- a bound one lost piece product exceeds (test_x6_model_cpu.py);
+// a power-of-two rescaling of data against fc1.weight changes no bit; the all-fp32 variant
+// (DLAMD_MLP_L1=fp32) meets the same bound.
 #include "dl_internal.h"
 
 #include <type_traits>

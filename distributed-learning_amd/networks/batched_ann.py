@@ -180,7 +180,7 @@ class BatchedANN:
         return self.loss
 
     # -------------------------------------------------------------- evaluation
-    def evaluate(self, X, data, labels, logits=None, row_splits=0):
+    def evaluate(self, X, data, labels, logits=None, row_splits=0, fused=None):
         """Every agent's model on a test set, forward only: returns (loss[N] fp32 mean
         cross-entropy, correct[N] int32 rows whose logit argmax is the label) -- the per-node
         ``accuracy ..., loss ...`` of the reference's MasterNode (Man_Colab.ipynb cells 21-23)
@@ -192,7 +192,9 @@ class BatchedANN:
         logits: optional fp32 [N, R, output_dim] output whose last dimension is contiguous (a
         view of a wider buffer is fine; columns past output_dim are never written);
         row_splits: workgroups per agent, 0 = chosen; a performance hint, any value gives the
-        same bits.
+        same bits;
+        fused: None = ``dl_mlp_eval`` wherever it covers the call (below), False = the layered
+        forward (row-major X only), True = ``dl_mlp_eval`` or a ValueError.
 
         The returned tensors are this object's, overwritten by the next call.  Shapes the kernel
         refuses (``eval_supported``; row-major X only) run the forward as four ``dl_bgemm``
@@ -238,10 +240,12 @@ class BatchedANN:
         loss, correct = self.eval_out if labels is not None else (None, None)
         kernel = eval_supported(din, dh, dout) and (
             tiled or (X.data_ptr() % 16 == 0 and ldx % 4 == 0 and data.data_ptr() % 16 == 0))
-        if not kernel:
+        if fused and not kernel:
+            raise ValueError("dl_mlp_eval does not cover these shapes or alignments")
+        if not kernel or (fused is not None and not fused):
             if tiled:
-                raise ValueError("the column-tiled layout needs shapes dl_mlp_eval covers "
-                                 "(eval_supported)")
+                raise ValueError("the column-tiled layout needs dl_mlp_eval: shapes it covers "
+                                 "(eval_supported) and no fused=False")
             self._evaluate_layers(X, data, labels, logits, R, loss, correct)
             return loss, correct
         lib = _lib.load()

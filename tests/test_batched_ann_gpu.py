@@ -1,5 +1,7 @@
 """Batched per-agent MLP gradients (config c3) against plain PyTorch fp32 autograd, one
-ANNModel per agent (reference networks/ann_model.py + torch.nn.CrossEntropyLoss)."""
+ANNModel per agent (reference networks/ann_model.py + torch.nn.CrossEntropyLoss).
+The fused path's tight bound (fp32 rounding level, per parameter block, against float64) lives in
+tests/test_mlp_x6_gpu.py."""
 import numpy as np
 import pytest
 import torch

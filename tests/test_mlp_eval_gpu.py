@@ -1,6 +1,7 @@
 """dl_mlp_eval (BatchedANN.evaluate, MLPConsensusSGD.evaluate): every agent's test loss, correct
 count and logits in one launch, against the project's ANNModel run in fp64 on the CPU and, bit
-for bit, against the loss of the gradient kernel whose forward it shares."""
+for bit, against the loss of the gradient kernel whose forward it shares.
+The logits' tight bound (fp32 rounding level, per agent) lives in tests/test_mlp_x6_gpu.py."""
 import copy
 import functools
 
@@ -179,7 +180,8 @@ def test_containment(cuda, rows):
 
 
 def test_layered_fallback(cuda):
-    """Shapes the kernel refuses (input_dim % 4 != 0) run the dl_bgemm forward."""
+    """Shapes the kernel refuses (input_dim % 4 != 0) run the dl_bgemm forward, and so does
+    evaluate(fused=False) on any row-major call."""
     from distributed_learning_amd.networks.batched_ann import BatchedANN
     n, rows, dims = 4, 100, (50, 40, 7)
     for shared in (True, False):
@@ -190,6 +192,28 @@ def test_layered_fallback(cuda):
                                       c["labels"].to(cuda), logits=logits)
         assert bann.eval_ws is None                     # no kernel workspace: the layered path
         check_against_fp64(c, c["labels"], loss, correct, logits)
+        with pytest.raises(ValueError):
+            bann.evaluate(padded_rows(c["X0"], cuda), c["data"].to(cuda), c["labels"].to(cuda),
+                          fused=True)
+    # fused=False: the layered forward on a shape the kernel covers (fused=None and True: the
+    # kernel); the tiled layout has no layered forward
+    n, rows, dims = 3, 200, (52, 40, 7)
+    c = case(n, rows, dims, True)
+    bann = BatchedANN(n, 64, *dims, device=cuda)
+    X, data, labels = padded_rows(c["X0"], cuda), c["data"].to(cuda), c["labels"].to(cuda)
+    logits = torch.full((n, rows, dims[2]), float("nan"), device=cuda)
+    loss, correct = bann.evaluate(X, data, labels, logits=logits, fused=False)
+    assert bann.eval_ws is None
+    check_against_fp64(c, c["labels"], loss, correct, logits)
+    kl = torch.full_like(logits, float("nan"))
+    bann.evaluate(X, data, labels, logits=kl, fused=True)
+    assert bann.eval_ws is not None
+    kn = torch.full_like(logits, float("nan"))
+    bann.evaluate(X, data, labels, logits=kn)
+    assert torch.equal(kn, kl)
+    with pytest.raises(ValueError):
+        from distributed_learning_amd import engine
+        bann.evaluate(engine.to_tiled(c["X0"].to(cuda), 64), data, labels, fused=False)
 
 
 @pytest.mark.parametrize("layout", ["rows", "tiled"])
