@@ -1,10 +1,13 @@
 // C ABI of libdlamd.so (include/dlamd.h): the thread-local error, the device's compute units and
-// the environment knobs, read once per call.  What a round entry point checks and launches is
-// decided by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here
-// their description of a call is turned into launch_* calls and the step after them.  The entry
-// points that are no rounds (dl_mix_until, dl_consensus_gd, the conversions, ...) check their
-// own arguments.  No exceptions cross this boundary; every entry point returns a dl_status and
-// leaves a thread-local message for dl_last_error().
+// the environment knobs, read once per call.  What an entry point checks and launches is decided
+// by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here their
+// description of a call is turned into launch_* calls and the step after them.  Shaped there:
+// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round), the one-pass
+// deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch, dl_lenet_grad
+// and dl_lenet_eval.  The others (dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
+// deviation, the conversions, the step-rows functions, ...) check their own arguments here:
+// their LDS-size functions live in kernel files.  No exceptions cross this boundary; every entry
+// point returns a dl_status and leaves a thread-local message for dl_last_error().
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -131,6 +134,9 @@ int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, cons
             case dl::kLaunchTile:
                 e = dl::launch_mix_tile(l.t, l.chunks, l.sgd, l.dev, l.mix, l.grid, l.lds, l.fast,
                                         s);
+                break;
+            case dl::kLaunchSgdTile:
+                e = dl::launch_mix_sgd_tile(l.t, l.q, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
                 break;
             case dl::kLaunchTileReg:
                 e = dl::launch_mix_tile_reg(l.t, l.chunks, l.head, l.tail_fmt, l.sgd, l.dev, l.grid,
@@ -663,111 +669,23 @@ int dl_sgd_step(const dl_sgd_args *a, dl_stream_t stream) {
     return e == hipSuccess ? DL_OK : hip_fail(e, "sgd_step launch");
 }
 
-namespace {
-// dl_sgd_round / dl_sgd_round_plan: everything that needs no device, in the header's order
-int check_sgd_round(const dl_sgd_round_args *a) {
-    if (!a) return fail(DL_ERR_INVALID, "dl_sgd_round: args is NULL");
-    const dl_mix_args &m = a->mix;
-    if (!m.x || !m.y || !m.g) return fail(DL_ERR_INVALID, "dl_sgd_round: null x/y/g");
-    if (m.halo || m.n_halo != 0 || m.mean_prev || m.colsum_out || m.n_local_src != 0 ||
-        m.n_halo_blocks != 0 || m.partial_rows_out)
-        return fail(DL_ERR_UNSUPPORTED, "dl_sgd_round: no halo rows, partition row sets or lagged "
-                                        "deviation (halo, n_halo, mean_prev, colsum_out, "
-                                        "n_local_src, n_halo_blocks, partial_rows_out must be "
-                                        "NULL / 0)");
-    char err[dl::kErrLen];
-    int rc = dl::check_mix_args(&m, err, true);
-    if (rc) return status(rc, err);
-    const bool tiled = m.tile_cols > 0;
-    const int64_t n = m.W.n_rows;
-    if (a->momentum != 0.f &&
-        (!a->buf || (tiled ? a->ldb < 0 || (a->ldb > 0 && a->ldb < n) || a->ldb > 65535 * 4
-                           : a->ldb < m.n_params)))
-        return fail(DL_ERR_INVALID, "dl_sgd_round: momentum needs a buffer laid out as x "
-                                    "(row-major ldb >= n_params; column-tiled ldb 0 or >= n_rows)");
-    if (a->nesterov && (a->momentum <= 0.f || a->dampening != 0.f))
-        return fail(DL_ERR_INVALID, "dl_sgd_round: Nesterov momentum requires a momentum and zero "
-                                    "dampening");
-    if (a->momentum != 0.f) {
-        const int64_t Tc = m.tile_cols;
-        const int64_t ntl = tiled ? (m.n_params + Tc - 1) / Tc : 0;
-        auto extent = [&](int64_t ld) {
-            return tiled ? (size_t)(((ntl - 1) * (ld ? ld : n) + n) * Tc * 4)
-                         : ((size_t)(n - 1) * ld + m.n_params) * 4;
-        };
-        const size_t bb = extent(a->ldb);
-        if (overlaps(a->buf, bb, m.x, extent(m.ldx)) || overlaps(a->buf, bb, m.y, extent(m.ldy)) ||
-            overlaps(a->buf, bb, m.g, extent(m.ldg)))
-            return fail(DL_ERR_INVALID, "dl_sgd_round: buf overlaps x, y or g");
-    }
-    return DL_OK;
-}
-
-// do the float4 kernels reach the momentum buffers: 16-byte aligned, and row-major rows too,
-// within the 32-bit offsets of a tile base (as launch.cpp tile_args asks of x, g and y)
-bool sgd_buf_vec(const dl_sgd_round_args *a) {
-    if (a->momentum == 0.f) return true;
-    if (!aligned16(a->buf)) return false;
-    if (a->mix.tile_cols > 0) return true;
-    return a->ldb % 4 == 0 &&
-           ((int64_t)(a->mix.W.n_rows - 1) * a->ldb + 128) * 4 < ((int64_t)1 << 32);
-}
-}  // namespace
-
 int dl_sgd_round_plan(const dl_sgd_round_args *args, dl_mix_plan *plan) {
     g_err.clear();
-    int rc = check_sgd_round(args);
-    if (rc) return rc;
-    if (!plan) return fail(DL_ERR_INVALID, "dl_sgd_round_plan: plan is NULL");
-    Plan pl;
-    rc = plan_mix(&args->mix, &pl);
-    if (rc) return rc;
-    if (pl.pub.path != 1)
-        return fail(DL_ERR_UNSUPPORTED, "dl_sgd_round: the fused momentum round runs on the LDS "
-                                        "tile kernel (plan path 1); this round plans path %d",
-                    pl.pub.path);
-    *plan = pl.pub;
-    return DL_OK;
+    char err[dl::kErrLen];
+    return status(dl::shape_sgd_round(args, device_cus(), dl::read_knobs(), nullptr, 0, plan,
+                                      nullptr, err), err);
 }
 
 int dl_sgd_round(const dl_sgd_round_args *args, void *workspace, size_t ws_bytes,
                  dl_stream_t stream) {
-    dl_mix_plan plan;
-    int rc = dl_sgd_round_plan(args, &plan);
-    if (rc) return rc;
-    const dl_mix_args &m = args->mix;
+    g_err.clear();
     dl::Launches L;
     char err[dl::kErrLen];
-    rc = dl::shape_round(m, device_cus(), dl::read_knobs(), workspace, ws_bytes, &L, err,
-                         sgd_buf_vec(args));
+    const int rc = dl::shape_sgd_round(args, device_cus(), dl::read_knobs(), workspace, ws_bytes,
+                                       nullptr, &L, err);
     if (rc) return status(rc, err);
-    for (int i = 0; i < L.n; ++i)
-        if (L.l[i].kind != dl::kLaunchTile)
-            return fail(DL_ERR_UNSUPPORTED, "dl_sgd_round: the fused momentum round runs on the "
-                                            "LDS tile kernel (plan path 1) only");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int i = 0; i < L.n; ++i) {
-        const dl::Launch &l = L.l[i];
-        dl::SgdTileArgs q{};
-        q.p = dl::SgdParams{m.lr, args->momentum, args->dampening, args->weight_decay,
-                            args->first ? 1 : 0, args->nesterov ? 1 : 0};
-        if (args->momentum != 0.f) {
-            q.buf = args->buf;
-            q.ldb = args->ldb;
-            dl::tile_stride(l.t.tiled, args->ldb, l.t.n_rows, 4 * l.chunks, &q.bts, &q.brs);
-        }
-        hipError_t e = dl::launch_mix_sgd_tile(l.t, q, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
-        if (e != hipSuccess)
-            return fail(DL_ERR_HIP, "mix_sgd_tile_kernel%s launch: %s (%d)",
-                        l.fast ? "" : " (tail)", hipGetErrorString(e), (int)e);
-    }
-    if (L.after == dl::kAfterZero) return zero_deviation(m.W.n_rows, m.dev_sq, m.dev_max, s);
-    if (L.after == dl::kAfterReduce) {
-        hipError_t e = dl::launch_dev_reduce(L.partial, L.parts, L.rows, m.dev_sq, m.dev_max, s,
-                                             L.max_zeroed);
-        if (e != hipSuccess) return hip_fail(e, "dev_reduce launch");
-    }
-    return DL_OK;
+    return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, "mix_sgd_tile_kernel",
+               static_cast<hipStream_t>(stream));
 }
 
 size_t dl_mlp_workspace_bytes(int32_t n_agents) {
@@ -776,47 +694,15 @@ size_t dl_mlp_workspace_bytes(int32_t n_agents) {
 
 int dl_mlp_grad(const dl_mlp_args *a, dl_stream_t stream) {
     g_err.clear();
-    if (!a) return fail(DL_ERR_INVALID, "dl_mlp_grad: null args");
+    char err[dl::kErrLen];
+    const int rc = dl::shape_mlp_grad(a, err);
+    if (rc) return status(rc, err);
     if (a->n_agents == 0) return DL_OK;
-    if (!dl::mlp_fused_supported(a->batch, a->input_dim, a->hidden_dim, a->output_dim))
-        return fail(DL_ERR_UNSUPPORTED, "dl_mlp_grad: fused path needs batch 64, input_dim %% 4 "
-                                        "== 0, even hidden_dim <= 152, output_dim <= 16 (got %d, "
-                                        "%d, %d, %d)", a->batch, a->input_dim, a->hidden_dim,
-                    a->output_dim);
-    const int64_t din = a->input_dim, dh = a->hidden_dim, dout = a->output_dim;
-    const int64_t P = dh * din + dh + 2 * (dh * dh + dh) + dout * dh + dout;
-    const int32_t T = a->tile_cols;
-    if (T < 0 || (T > 0 && (T < 4 || (T & (T - 1)) || (int64_t)T * a->n_agents > 0x7fffffff)))
-        return fail(DL_ERR_INVALID, "dl_mlp_grad: tile_cols must be 0 or a power of two >= 4");
-    if (a->n_agents < 0 || a->n_agents > 65535 || !a->X || !a->data || !a->labels || !a->G ||
-        (T == 0 && (a->ldx < P || a->ldg < P)) || a->s_data < (int64_t)a->batch * din ||
-        a->s_labels < a->batch)
-        return fail(DL_ERR_INVALID, "dl_mlp_grad: bad arguments (agents %d, params %lld, ldx %lld, "
-                                    "ldg %lld)", a->n_agents, (long long)P, (long long)a->ldx,
-                    (long long)a->ldg);
-    if (!aligned16(a->X) || !aligned16(a->data) || !aligned16(a->G) ||
-        (T == 0 && ((a->ldx & 3) || (a->ldg & 3))) || (a->s_data & 3))
-        return fail(DL_ERR_INVALID, "dl_mlp_grad: X, data, G must be 16-byte aligned with row "
-                                    "strides % 4 == 0");
-    const size_t tb = T ? (size_t)((P + T - 1) / T) * T * a->n_agents * 4 : 0;
-    if (T && tb / 4 > 0x7fffffff)   // the kernel addresses an agent's tiled row with 32-bit offsets
-        return fail(DL_ERR_UNSUPPORTED, "dl_mlp_grad: tiled X too large for 32-bit offsets");
-    const size_t xb = T ? tb : ((size_t)a->n_agents - 1) * a->ldx * 4 + P * 4;
-    const size_t gb = T ? tb : ((size_t)a->n_agents - 1) * a->ldg * 4 + P * 4;
-    if (overlaps(a->X, xb, a->G, gb)) return fail(DL_ERR_INVALID, "dl_mlp_grad: G overlaps X");
-    if (a->out_mode != 0 && a->out_mode != 1)
-        return fail(DL_ERR_INVALID, "dl_mlp_grad: out_mode must be 0 (gradient) or 1 (step)");
-    if (a->out_mode == 1 && T == 0 && a->ldg != a->ldx)
-        return fail(DL_ERR_INVALID, "dl_mlp_grad: out_mode 1 needs ldg == ldx");
-    if (a->workspace && (!aligned16(a->workspace) ||
-                         overlaps(a->workspace, dl_mlp_workspace_bytes(a->n_agents), a->X, xb) ||
-                         overlaps(a->workspace, dl_mlp_workspace_bytes(a->n_agents), a->G, gb)))
-        return fail(DL_ERR_INVALID, "dl_mlp_grad: workspace must be 16-byte aligned and disjoint "
-                                    "from X and G");
     hipError_t e = dl::launch_mlp_fused(a->X, a->ldx, a->data, a->s_data, a->labels, a->s_labels,
                                         a->G, a->ldg, a->loss, a->n_agents, a->input_dim,
-                                        a->hidden_dim, a->output_dim, T, a->out_mode == 1,
-                                        a->lr, a->workspace, static_cast<hipStream_t>(stream));
+                                        a->hidden_dim, a->output_dim, a->tile_cols,
+                                        a->out_mode == 1, a->lr, a->workspace,
+                                        static_cast<hipStream_t>(stream));
     return e == hipSuccess ? DL_OK : hip_fail(e, "mlp_fused launch");
 }
 
@@ -882,7 +768,22 @@ size_t dl_lenet_workspace_bytes(int32_t n_agents, int32_t batch, int32_t num_cla
 }
 
 namespace {
-// dl_lenet_grad's launches in order; with events, one recorded before each and one after the last
+hipError_t lenet_launch(const dl::LenetPlan &pl, const dl::LenetStep &st, hipStream_t s) {
+    const dl::XentArgs &h = st.head;
+    switch (st.kind) {
+        case dl::kLenetConvFwd: return dl::launch_lenet_conv_fwd(pl.conv, pl.fwd_grid, s);
+        case dl::kLenetGemm: return dl::launch_bgemm(st.gemm, s);
+        case dl::kLenetHead:
+            return dl::launch_xent_grad(h.Z, h.sZ, h.y, h.sY, h.dZ, h.sD, h.loss, h.batch, h.rows,
+                                        h.classes, s);
+        case dl::kLenetConvBwd: return dl::launch_lenet_conv_bwd(pl.conv, pl.bwd_grid, s);
+        case dl::kLenetConvReduce: return dl::launch_lenet_conv_reduce(pl.conv, pl.n_agents, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// dl_lenet_grad's launches as shape_lenet lists them; with events, one recorded before each and
+// one after the last.  After a failure nothing more is launched or recorded.
 int lenet_run(const dl_lenet_args *a, void *workspace, size_t ws_bytes, hipStream_t s,
               void *const *events, int32_t n_events, int32_t *n_launches) {
     g_err.clear();
@@ -894,92 +795,11 @@ int lenet_run(const dl_lenet_args *a, void *workspace, size_t ws_bytes, hipStrea
     if (events && n_events < pl.n_launches + 1)
         return fail(DL_ERR_INVALID, "dl_lenet_grad_events: needs %d events (got %d)",
                     pl.n_launches + 1, n_events);
-    const int32_t N = a->n_agents, B = a->batch, nc = a->num_classes;
-    char *ws = static_cast<char *>(workspace);
-    auto f = [&](size_t off) { return reinterpret_cast<float *>(ws + off); };
-    float *pool2 = f(pl.ws.pool2), *h1 = f(pl.ws.h1), *h2 = f(pl.ws.h2), *z = f(pl.ws.z);
-    float *dz3 = f(pl.ws.dz3), *dz2 = f(pl.ws.dz2), *dz1 = f(pl.ws.dz1), *da = f(pl.ws.da);
-    const dl::LenetConvArgs cv{a->X, a->ldx, a->data, a->s_data, f(pl.ws.pool1),
-                               reinterpret_cast<uint8_t *>(ws + pl.ws.code1), pool2,
-                               reinterpret_cast<uint8_t *>(ws + pl.ws.code2), da, f(pl.ws.part),
-                               a->G, a->ldg, B, pl.train, pl.passes, pl.fwd_wpa, pl.groups,
-                               pl.bwd_wpa};
-    int n = 0;
     hipError_t e = hipSuccess;
-    auto mark = [&]() {   // before a launch (and after the last)
-        if (events && e == hipSuccess) e = hipEventRecord(static_cast<hipEvent_t>(events[n]), s);
-        ++n;
-    };
-    // C[b] (M x Nn) = op(A) op(B) per agent; operands with their row and agent strides
-    auto gemm = [&](int M, int Nn, int K, const float *A, int64_t lda, int64_t sA, int ta,
-                    const float *Bm, int64_t ldb, int64_t sB, int tb, float *C, int64_t ldc,
-                    int64_t sC, int epi, const float *bias, const float *H, int64_t ldh,
-                    float *rowsum, bool xent_loss) {
-        mark();
-        if (e != hipSuccess) return;
-        dl::BgemmArgs p{};
-        p.batch = N; p.M = M; p.N = Nn; p.K = K;
-        p.A = A; p.lda = lda; p.sA = sA; p.ta = ta;
-        p.B = Bm; p.ldb = ldb; p.sB = sB; p.tb = tb;
-        p.C = C; p.ldc = ldc; p.sC = sC;
-        p.epi = epi; p.bias = bias; p.sBias = a->ldx;
-        p.H = H; p.ldh = ldh; p.sH = (int64_t)B * ldh;
-        p.rowsum = rowsum; p.sR = a->ldg;
-        if (epi == dl::EPI_BIAS_XENT) {
-            p.labels = a->labels; p.sLab = a->s_labels;
-            p.loss = xent_loss ? a->loss : nullptr;
-        }
-        e = dl::launch_bgemm(p, s);
-    };
-    const float *X = a->X;
-    float *G = a->G;
-    const int64_t ldx = a->ldx, ldg = a->ldg;
-    const int F1 = dl::kLenetFc1, F2 = dl::kLenetFc2, P2 = dl::kLenetPool2;
-    const int64_t fc3b = dl::kLenetFc3W + 84 * (int64_t)nc;
-    mark();
-    if (e == hipSuccess) e = dl::launch_lenet_conv_fwd(cv, pl.fwd_grid, s);
-    gemm(B, F1, P2, pool2, P2, (int64_t)B * P2, 0, X + dl::kLenetFc1W, P2, ldx, 1, h1, F1,
-         (int64_t)B * F1, dl::EPI_BIAS_RELU, X + dl::kLenetFc1B, nullptr, 0, nullptr, false);
-    gemm(B, F2, F1, h1, F1, (int64_t)B * F1, 0, X + dl::kLenetFc2W, F1, ldx, 1, h2, F2,
-         (int64_t)B * F2, dl::EPI_BIAS_RELU, X + dl::kLenetFc2B, nullptr, 0, nullptr, false);
-    if (a->logits)
-        gemm(B, nc, F2, h2, F2, (int64_t)B * F2, 0, X + dl::kLenetFc3W, F2, ldx, 1, a->logits,
-             a->ldz, a->s_logits, dl::EPI_BIAS, X + fc3b, nullptr, 0, nullptr, false);
-    if (pl.head == 1) {
-        gemm(B, nc, F2, h2, F2, (int64_t)B * F2, 0, X + dl::kLenetFc3W, F2, ldx, 1, dz3, nc,
-             (int64_t)B * nc, dl::EPI_BIAS_XENT, X + fc3b, nullptr, 0, nullptr, true);
-    } else if (pl.head == 2) {
-        gemm(B, nc, F2, h2, F2, (int64_t)B * F2, 0, X + dl::kLenetFc3W, F2, ldx, 1, z, nc,
-             (int64_t)B * nc, dl::EPI_BIAS, X + fc3b, nullptr, 0, nullptr, false);
-        mark();
-        if (e == hipSuccess)
-            e = dl::launch_xent_grad(z, (int64_t)B * nc, a->labels, a->s_labels, dz3,
-                                     (int64_t)B * nc, a->loss, N, B, nc, s);
+    for (int i = 0; e == hipSuccess && i <= pl.n_launches; ++i) {
+        if (events) e = hipEventRecord(static_cast<hipEvent_t>(events[i]), s);
+        if (e == hipSuccess && i < pl.n_launches) e = lenet_launch(pl, pl.step[i], s);
     }
-    if (pl.train) {
-        // weight gradients dZ^T . (layer input) straight into G, bias gradients as row sums;
-        // dZ of the layer below through the weights, times ReLU's derivative
-        gemm(nc, F2, B, dz3, nc, (int64_t)B * nc, 1, h2, F2, (int64_t)B * F2, 0,
-             G + dl::kLenetFc3W, F2, ldg, dl::EPI_NONE, nullptr, nullptr, 0, G + fc3b, false);
-        gemm(B, F2, nc, dz3, nc, (int64_t)B * nc, 0, X + dl::kLenetFc3W, F2, ldx, 0, dz2, F2,
-             (int64_t)B * F2, dl::EPI_DRELU, nullptr, h2, F2, nullptr, false);
-        gemm(F2, F1, B, dz2, F2, (int64_t)B * F2, 1, h1, F1, (int64_t)B * F1, 0,
-             G + dl::kLenetFc2W, F1, ldg, dl::EPI_NONE, nullptr, nullptr, 0,
-             G + dl::kLenetFc2B, false);
-        gemm(B, F1, F2, dz2, F2, (int64_t)B * F2, 0, X + dl::kLenetFc2W, F1, ldx, 0, dz1, F1,
-             (int64_t)B * F1, dl::EPI_DRELU, nullptr, h1, F1, nullptr, false);
-        gemm(F1, P2, B, dz1, F1, (int64_t)B * F1, 1, pool2, P2, (int64_t)B * P2, 0,
-             G + dl::kLenetFc1W, P2, ldg, dl::EPI_NONE, nullptr, nullptr, 0,
-             G + dl::kLenetFc1B, false);
-        // the gradient entering the second pooling: dZ1 . fc1.weight
-        gemm(B, P2, F1, dz1, F1, (int64_t)B * F1, 0, X + dl::kLenetFc1W, P2, ldx, 0, da, P2,
-             (int64_t)B * P2, dl::EPI_NONE, nullptr, nullptr, 0, nullptr, false);
-        mark();
-        if (e == hipSuccess) e = dl::launch_lenet_conv_bwd(cv, pl.bwd_grid, s);
-        mark();
-        if (e == hipSuccess) e = dl::launch_lenet_conv_reduce(cv, N, s);
-    }
-    mark();   // after the last launch
     return e == hipSuccess ? DL_OK : hip_fail(e, "lenet launch");
 }
 }  // namespace
@@ -1043,33 +863,10 @@ int dl_stream_copy(const float *src, float *dst, int64_t n_floats, int32_t varia
 
 int dl_bgemm(const dl_bgemm_args *a, dl_stream_t stream) {
     g_err.clear();
-    if (!a || a->batch <= 0 || a->M <= 0 || a->N <= 0 || a->K <= 0 || !a->A || !a->B || !a->C ||
-        a->batch > 65535 || a->epi < DL_EPI_NONE || a->epi > DL_EPI_BIAS_XENT)
-        return fail(DL_ERR_INVALID, "dl_bgemm: bad sizes/pointers/epilogue");
-    if ((a->ta ? a->lda < a->M : a->lda < a->K) || (a->tb ? a->ldb < a->K : a->ldb < a->N) ||
-        a->ldc < a->N)
-        return fail(DL_ERR_INVALID, "dl_bgemm: leading dimension too small");
-    if (a->epi >= DL_EPI_DRELU && a->epi <= DL_EPI_DELU && (!a->H || a->ldh < a->N))
-        return fail(DL_ERR_INVALID, "dl_bgemm: derivative epilogue needs H with ldh >= N");
-    if (a->epi == DL_EPI_BIAS_XENT && (a->M > 64 || a->N > 64 || !a->labels))
-        return fail(DL_ERR_INVALID, "dl_bgemm: cross-entropy epilogue needs M <= 64 rows, "
-                                    "N <= 64 classes and labels");
-    // output batches must not overlap: two workgroups would write the same floats (input
-    // strides may be 0, a shared operand)
-    if (a->batch > 1 && (a->sC < (int64_t)(a->M - 1) * a->ldc + a->N ||
-                         (a->rowsum && a->s_rowsum < a->M)))
-        return fail(DL_ERR_INVALID, "dl_bgemm: output batch stride smaller than one batch "
-                                    "(sC >= (M-1)*ldc + N, s_rowsum >= M)");
-    dl::BgemmArgs p{};
-    p.batch = a->batch; p.M = a->M; p.N = a->N; p.K = a->K;
-    p.A = a->A; p.lda = a->lda; p.sA = a->sA; p.ta = a->ta;
-    p.B = a->B; p.ldb = a->ldb; p.sB = a->sB; p.tb = a->tb;
-    p.C = a->C; p.ldc = a->ldc; p.sC = a->sC;
-    p.epi = a->epi; p.bias = a->bias; p.sBias = a->s_bias;
-    p.H = a->H; p.ldh = a->ldh; p.sH = a->sH;
-    p.rowsum = a->rowsum; p.sR = a->s_rowsum;
-    p.labels = a->labels; p.sLab = a->s_labels; p.loss = a->loss;
-    hipError_t e = dl::launch_bgemm(p, static_cast<hipStream_t>(stream));
+    char err[dl::kErrLen];
+    const int rc = dl::check_bgemm(a, err);
+    if (rc) return status(rc, err);
+    hipError_t e = dl::launch_bgemm(dl::bgemm_args(*a), static_cast<hipStream_t>(stream));
     return e == hipSuccess ? DL_OK : hip_fail(e, "bgemm launch");
 }
 

@@ -5,8 +5,7 @@
 
 #include <cstdlib>
 
-#include "launch.h"   // TileArgs; plan.h: the tile geometry shared with the planner
-#include "sgd_elem.h"  // SgdParams
+#include "launch.h"   // the kernels' parameters; plan.h: the tile geometry shared with the planner
 
 namespace dl {
 
@@ -33,16 +32,8 @@ hipError_t launch_mix_gather(const TileArgs &a, bool sgd, bool columns, hipStrea
 hipError_t launch_mix_tile_reg(const TileArgs &a, int chunks, int head, int tail_fmt, bool sgd,
                                bool dev, int grid, int lds, hipStream_t s);
 // The fused momentum-SGD round's tile kernel (mix_sgd.hip) for one launch of a path-1 round
-// shaped by shape_round: TileArgs as for launch_mix_tile (g required, no halo rows, no row set),
-// plus the momentum buffers -- laid out as x, with their FAST-path strides (launch.h
-// tile_stride) -- and the optimizer's parameters.  buf is read only when mu != 0.
-struct SgdTileArgs {
-    float *buf;
-    int64_t ldb;
-    int64_t bts;    // FAST-path tile stride in bytes
-    uint32_t brs;   // FAST-path row stride in bytes
-    SgdParams p;
-};
+// shaped by shape_sgd_round: TileArgs as for launch_mix_tile (g required, no halo rows, no row
+// set), plus the momentum buffers and the optimizer's parameters (launch.h SgdTileArgs).
 hipError_t launch_mix_sgd_tile(const TileArgs &a, const SgdTileArgs &q, int chunks, bool dev,
                                int grid, int lds_bytes, bool fast, hipStream_t s);
 // K rounds of mixing on LDS-resident tiles (mix_multi.hip); FAST tiles only, no halo rows
@@ -161,51 +152,16 @@ struct GdArgs {
 int64_t gd_lds_bytes(int n_agents, int n_features, int rows, bool x_in_lds, int64_t *x_off);
 hipError_t launch_consensus_gd(const GdArgs &a, int lds_bytes, hipStream_t s);
 
-enum Epi {
-    EPI_NONE = 0,
-    EPI_BIAS = 1,
-    EPI_BIAS_RELU = 2,
-    EPI_BIAS_TANH = 3,
-    EPI_BIAS_ELU = 4,
-    EPI_DRELU = 5,
-    EPI_DTANH = 6,
-    EPI_DELU = 7,
-    EPI_BIAS_XENT = 8
-};
-
-struct BgemmArgs {
-    int32_t batch, M, N, K;
-    const float *A;
-    int64_t lda, sA;
-    int32_t ta;
-    const float *B;
-    int64_t ldb, sB;
-    int32_t tb;
-    float *C;
-    int64_t ldc, sC;
-    int32_t epi;
-    const float *bias;
-    int64_t sBias;
-    const float *H;
-    int64_t ldh, sH;
-    float *rowsum;
-    int64_t sR;
-    const int32_t *labels;
-    int64_t sLab;
-    float *loss;
-};
 hipError_t launch_bgemm(const BgemmArgs &p, hipStream_t s);
 hipError_t launch_xent_grad(const float *Z, int64_t sZ, const int32_t *y, int64_t sY, float *dZ,
                             int64_t sD, float *loss, int batch, int rows, int classes,
                             hipStream_t s);
 
-int mlp_fused_supported(int batch, int din, int dh, int dout);
 hipError_t launch_mlp_fused(const float *X, int64_t ldx, const float *data, int64_t s_data,
                             const int32_t *labels, int64_t s_lab, float *G, int64_t ldg,
                             float *loss, int n_agents, int din, int dh, int dout, int tile_cols,
                             bool step, float lr, float *ws, hipStream_t s);
-// the split gradient path's workspace (dl_mlp_args.workspace), in floats
-size_t mlp_workspace_floats(int n_agents);
+// ws: the split gradient path's workspace (launch.h mlp_workspace_floats), nullable
 
 // dl_mlp_eval's kernel parameter (mlp_fused.hip mlp_eval_kernel), after launch.h shape_mlp_eval
 struct MlpEvalArgs {
@@ -241,24 +197,7 @@ hipError_t launch_batch_gather(const BatchGatherPlan &p, int32_t *advance, hipSt
 // batch and, with `advance` (the cursor, writable), the one-thread launch that steps it
 hipError_t launch_image_batch(const ImageBatchPlan &p, int32_t *advance, hipStream_t s);
 
-// dl_lenet_grad's convolution kernels (lenet.hip) as launch.h shape_lenet shaped them.  The
-// workspace pointers are the regions of LenetWs (agent stride batch x the per-image size).
-struct LenetConvArgs {
-    const float *X;          // parameter rows; the 2872 convolution parameters lead each
-    int64_t ldx;
-    const float *data;       // [batch][3][32][32] per agent
-    int64_t s_data;
-    float *pool1;            // [batch][1176]: written by the forward with train, read by the backward
-    uint8_t *code1;          // [batch][1176] winner codes, likewise
-    float *pool2;            // [batch][400]: fc1's input, always written
-    uint8_t *code2;          // [batch][400]
-    const float *da;         // [batch][400]: d loss / d pool2 (backward)
-    float *part;             // [groups][2872] per agent: the backward's group partials
-    float *G;                // the reduce's destination
-    int64_t ldg;
-    int32_t batch, train;
-    int32_t passes, fwd_wpa, groups, bwd_wpa;
-};
+// dl_lenet_grad's convolution kernels (lenet.hip) as launch.h shape_lenet shaped them.
 hipError_t launch_lenet_conv_fwd(const LenetConvArgs &p, int grid, hipStream_t s);
 hipError_t launch_lenet_conv_bwd(const LenetConvArgs &p, int grid, hipStream_t s);
 // G[a][j] = sum of agent a's group partials in group order, j < 2872

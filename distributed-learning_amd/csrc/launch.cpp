@@ -74,6 +74,22 @@ void reset(Launches *out) {
     std::memset(&out->l[0], 0, sizeof out->l[0]);
 }
 
+// No output (o) may share a byte with an input or another output; a span of 0 bytes is absent.
+struct Span { const void *p; size_t n; };
+int check_disjoint(const char *who, const Span *o, const char *const *o_name, int n_out,
+                   const Span *in, const char *const *in_name, int n_in, char *err) {
+    for (int i = 0; i < n_out; ++i) {
+        if (!o[i].n) continue;
+        for (int j = 0; j < n_in; ++j)
+            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
+                return fail(err, DL_ERR_INVALID, "%s: %s overlaps %s", who, o_name[i], in_name[j]);
+        for (int j = i + 1; j < n_out; ++j)
+            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
+                return fail(err, DL_ERR_INVALID, "%s: %s overlaps %s", who, o_name[i], o_name[j]);
+    }
+    return DL_OK;
+}
+
 void after_reduce(Launches *out, const float *partial, int parts, int rows, bool max_zeroed) {
     out->after = kAfterReduce;
     out->partial = partial;
@@ -370,6 +386,78 @@ int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_
     return DL_OK;
 }
 
+int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void *ws,
+                    size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    // the momentum round's own checks around the round's (y == x allowed)
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_sgd_round: args is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y || !m.g) return fail(err, DL_ERR_INVALID, "dl_sgd_round: null x/y/g");
+    if (m.halo || m.n_halo != 0 || m.mean_prev || m.colsum_out || m.n_local_src != 0 ||
+        m.n_halo_blocks != 0 || m.partial_rows_out)
+        return fail(err, DL_ERR_UNSUPPORTED,
+                    "dl_sgd_round: no halo rows, partition row sets or lagged deviation (halo, "
+                    "n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks, partial_rows_out "
+                    "must be NULL / 0)");
+    int rc = check_mix_args(&m, err, true);
+    if (rc) return rc;
+    const bool tiled = m.tile_cols > 0;
+    const int64_t n = m.W.n_rows;
+    if (a->momentum != 0.f &&
+        (!a->buf || (tiled ? a->ldb < 0 || (a->ldb > 0 && a->ldb < n) || a->ldb > 65535 * 4
+                           : a->ldb < m.n_params)))
+        return fail(err, DL_ERR_INVALID, "dl_sgd_round: momentum needs a buffer laid out as x "
+                                         "(row-major ldb >= n_params; column-tiled ldb 0 or >= "
+                                         "n_rows)");
+    if (a->nesterov && (a->momentum <= 0.f || a->dampening != 0.f))
+        return fail(err, DL_ERR_INVALID, "dl_sgd_round: Nesterov momentum requires a momentum and "
+                                         "zero dampening");
+    if (a->momentum != 0.f) {
+        const int64_t Tc = m.tile_cols;
+        const int64_t ntl = tiled ? (m.n_params + Tc - 1) / Tc : 0;
+        auto extent = [&](int64_t ld) {
+            return tiled ? (size_t)(((ntl - 1) * (ld ? ld : n) + n) * Tc * 4)
+                         : ((size_t)(n - 1) * ld + m.n_params) * 4;
+        };
+        const size_t bb = extent(a->ldb);
+        if (overlaps(a->buf, bb, m.x, extent(m.ldx)) || overlaps(a->buf, bb, m.y, extent(m.ldy)) ||
+            overlaps(a->buf, bb, m.g, extent(m.ldg)))
+            return fail(err, DL_ERR_INVALID, "dl_sgd_round: buf overlaps x, y or g");
+    }
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_sgd_round_plan: plan is NULL");
+    Plan pl;
+    rc = plan_mix(m, n_cus, k, &pl, err);
+    if (rc) return rc;
+    if (pl.pub.path != 1)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_sgd_round: the fused momentum round runs on the "
+                                             "LDS tile kernel (plan path 1); this round plans "
+                                             "path %d", pl.pub.path);
+    if (plan) *plan = pl.pub;
+    if (!out) return DL_OK;
+    // do the float4 kernels reach the momentum buffers: 16-byte aligned, and row-major rows too,
+    // within the 32-bit offsets of a tile base (as tile_args asks of x, g and y)
+    const bool buf_vec =
+        a->momentum == 0.f ||
+        (aligned16(a->buf) && (tiled || (a->ldb % 4 == 0 &&
+                                         ((n - 1) * a->ldb + 128) * 4 < ((int64_t)1 << 32))));
+    rc = shape_round(m, n_cus, k, ws, ws_bytes, out, err, buf_vec);
+    if (rc) return rc;
+    for (int i = 0; i < out->n; ++i) {
+        Launch &l = out->l[i];
+        if (l.kind != kLaunchTile)
+            return fail(err, DL_ERR_UNSUPPORTED, "dl_sgd_round: the fused momentum round runs on "
+                                                 "the LDS tile kernel (plan path 1) only");
+        l.kind = kLaunchSgdTile;
+        l.q.p = SgdParams{m.lr, a->momentum, a->dampening, a->weight_decay,
+                          a->first ? 1 : 0, a->nesterov ? 1 : 0};
+        if (a->momentum != 0.f) {
+            l.q.buf = a->buf;
+            l.q.ldb = a->ldb;
+            tile_stride(l.t.tiled, a->ldb, l.t.n_rows, 4 * l.chunks, &l.q.bts, &l.q.brs);
+        }
+    }
+    return DL_OK;
+}
+
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err) {
     reset(out);
@@ -496,12 +584,80 @@ int shape_deviation(const float *x, int64_t ldx, int32_t tile_cols, int32_t n_ro
     return DL_OK;
 }
 
+int shape_mlp_grad(const dl_mlp_args *a, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_mlp_grad: null args");
+    if (a->n_agents == 0) return DL_OK;
+    if (!mlp_fused_supported(a->batch, a->input_dim, a->hidden_dim, a->output_dim))
+        return fail(err, DL_ERR_UNSUPPORTED,
+                    "dl_mlp_grad: fused path needs batch 64, input_dim %% 4 == 0, even hidden_dim "
+                    "<= 152, output_dim <= 16 (got %d, %d, %d, %d)", a->batch, a->input_dim,
+                    a->hidden_dim, a->output_dim);
+    const int64_t din = a->input_dim, dh = a->hidden_dim, dout = a->output_dim;
+    const int64_t P = dh * din + dh + 2 * (dh * dh + dh) + dout * dh + dout;
+    const int32_t T = a->tile_cols;
+    if (T < 0 || (T > 0 && (T < 4 || (T & (T - 1)) || (int64_t)T * a->n_agents > 0x7fffffff)))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_grad: tile_cols must be 0 or a power of two >= 4");
+    if (a->n_agents < 0 || a->n_agents > 65535 || !a->X || !a->data || !a->labels || !a->G ||
+        (T == 0 && (a->ldx < P || a->ldg < P)) || a->s_data < (int64_t)a->batch * din ||
+        a->s_labels < a->batch)
+        return fail(err, DL_ERR_INVALID, "dl_mlp_grad: bad arguments (agents %d, params %lld, ldx "
+                                         "%lld, ldg %lld)", a->n_agents, (long long)P,
+                    (long long)a->ldx, (long long)a->ldg);
+    if (!aligned16(a->X) || !aligned16(a->data) || !aligned16(a->G) ||
+        (T == 0 && ((a->ldx & 3) || (a->ldg & 3))) || (a->s_data & 3))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_grad: X, data, G must be 16-byte aligned with row "
+                                         "strides %% 4 == 0");
+    const size_t tb = T ? (size_t)((P + T - 1) / T) * T * a->n_agents * 4 : 0;
+    if (T && tb / 4 > 0x7fffffff)   // the kernel addresses an agent's tiled row with 32-bit offsets
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_mlp_grad: tiled X too large for 32-bit offsets");
+    const size_t xb = T ? tb : ((size_t)a->n_agents - 1) * a->ldx * 4 + P * 4;
+    const size_t gb = T ? tb : ((size_t)a->n_agents - 1) * a->ldg * 4 + P * 4;
+    if (overlaps(a->X, xb, a->G, gb)) return fail(err, DL_ERR_INVALID, "dl_mlp_grad: G overlaps X");
+    if (a->out_mode != 0 && a->out_mode != 1)
+        return fail(err, DL_ERR_INVALID, "dl_mlp_grad: out_mode must be 0 (gradient) or 1 (step)");
+    if (a->out_mode == 1 && T == 0 && a->ldg != a->ldx)
+        return fail(err, DL_ERR_INVALID, "dl_mlp_grad: out_mode 1 needs ldg == ldx");
+    const size_t wb = mlp_workspace_floats(a->n_agents) * sizeof(float);
+    if (a->workspace && (!aligned16(a->workspace) || overlaps(a->workspace, wb, a->X, xb) ||
+                         overlaps(a->workspace, wb, a->G, gb)))
+        return fail(err, DL_ERR_INVALID, "dl_mlp_grad: workspace must be 16-byte aligned and "
+                                         "disjoint from X and G");
+    return DL_OK;
+}
+
+int check_bgemm(const dl_bgemm_args *a, char *err) {
+    if (!a || a->batch <= 0 || a->M <= 0 || a->N <= 0 || a->K <= 0 || !a->A || !a->B || !a->C ||
+        a->batch > 65535 || a->epi < DL_EPI_NONE || a->epi > DL_EPI_BIAS_XENT)
+        return fail(err, DL_ERR_INVALID, "dl_bgemm: bad sizes/pointers/epilogue");
+    if ((a->ta ? a->lda < a->M : a->lda < a->K) || (a->tb ? a->ldb < a->K : a->ldb < a->N) ||
+        a->ldc < a->N)
+        return fail(err, DL_ERR_INVALID, "dl_bgemm: leading dimension too small");
+    if (a->epi >= DL_EPI_DRELU && a->epi <= DL_EPI_DELU && (!a->H || a->ldh < a->N))
+        return fail(err, DL_ERR_INVALID, "dl_bgemm: derivative epilogue needs H with ldh >= N");
+    if (a->epi == DL_EPI_BIAS_XENT && (a->M > 64 || a->N > 64 || !a->labels))
+        return fail(err, DL_ERR_INVALID, "dl_bgemm: cross-entropy epilogue needs M <= 64 rows, "
+                                         "N <= 64 classes and labels");
+    // output batches must not overlap: two workgroups would write the same floats (input
+    // strides may be 0, a shared operand)
+    if (a->batch > 1 && (a->sC < (int64_t)(a->M - 1) * a->ldc + a->N ||
+                         (a->rowsum && a->s_rowsum < a->M)))
+        return fail(err, DL_ERR_INVALID, "dl_bgemm: output batch stride smaller than one batch "
+                                         "(sC >= (M-1)*ldc + N, s_rowsum >= M)");
+    return DL_OK;
+}
+
+BgemmArgs bgemm_args(const dl_bgemm_args &a) {   // the same fields in the same order
+    return BgemmArgs{a.batch, a.M, a.N, a.K, a.A, a.lda, a.sA, a.ta, a.B, a.ldb, a.sB, a.tb, a.C,
+                     a.ldc, a.sC, a.epi, a.bias, a.s_bias, a.H, a.ldh, a.sH, a.rowsum, a.s_rowsum,
+                     a.labels, a.s_labels, a.loss};
+}
+
 int shape_mlp_eval(const dl_mlp_eval_args *a, int n_cus, const void *ws, size_t ws_bytes,
                    bool check_ws, dl_mlp_eval_plan *out, char *err) {
     if (!a) return fail(err, DL_ERR_INVALID, "dl_mlp_eval: args is NULL");
     const int64_t din = a->input_dim, dh = a->hidden_dim, dout = a->output_dim, R = a->rows;
     // dl_mlp_grad's shape gate without the batch clause
-    if (din <= 0 || din % 4 || dh <= 0 || dh > 152 || dh % 2 || dout <= 0 || dout > 16 || R < 1)
+    if (!mlp_fused_supported(kMlpBatch, a->input_dim, a->hidden_dim, a->output_dim) || R < 1)
         return fail(err, DL_ERR_UNSUPPORTED,
                     "dl_mlp_eval: needs input_dim %% 4 == 0, even hidden_dim <= 152, output_dim "
                     "<= 16, rows >= 1 (got %d, %d, %d, rows %d)", a->input_dim, a->hidden_dim,
@@ -598,8 +754,6 @@ int shape_batch_gather(const dl_batch_gather_args *a, int n_cus, BatchGatherPlan
         return fail(err, DL_ERR_INVALID, "dl_batch_gather: advance must be 0 or 1");
     if (a->advance && !a->cursor)
         return fail(err, DL_ERR_INVALID, "dl_batch_gather: advance needs a cursor");
-    // no output may share a byte with an input or another output
-    struct Span { const void *p; size_t n; };
     const Span in[3] = {{a->samples, (size_t)((M - 1) * a->ld_samples + D) * 4},
                         {a->targets, a->targets ? (size_t)M * 4 : 0},
                         {a->index, (size_t)((N - 1) * a->s_index + S * B) * 4}};
@@ -608,17 +762,8 @@ int shape_batch_gather(const dl_batch_gather_args *a, int n_cus, BatchGatherPlan
                        {a->cursor, a->cursor ? (size_t)4 : 0}};
     static const char *const in_name[3] = {"samples", "targets", "index"};
     static const char *const out_name[3] = {"data", "labels", "cursor"};
-    for (int i = 0; i < 3; ++i) {
-        if (!o[i].n) continue;
-        for (int j = 0; j < 3; ++j)
-            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
-                return fail(err, DL_ERR_INVALID, "dl_batch_gather: %s overlaps %s", out_name[i],
-                            in_name[j]);
-        for (int j = i + 1; j < 3; ++j)
-            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
-                return fail(err, DL_ERR_INVALID, "dl_batch_gather: %s overlaps %s", out_name[i],
-                            out_name[j]);
-    }
+    if (const int rc = check_disjoint("dl_batch_gather", o, out_name, 3, in, in_name, 3, err))
+        return rc;
     if (!out) return DL_OK;
     BatchGatherPlan &p = *out;
     const int32_t dim4 = (int32_t)(D / 4);
@@ -701,8 +846,6 @@ int shape_image_batch(const dl_image_batch_args *a, int n_cus, ImageBatchPlan *o
         return fail(err, DL_ERR_INVALID, "dl_image_batch: advance must be 0 or 1");
     if (a->advance && !a->cursor)
         return fail(err, DL_ERR_INVALID, "dl_image_batch: advance needs a cursor");
-    // no output may share a byte with an input or another output
-    struct Span { const void *p; size_t n; };
     const Span in[5] = {{a->samples, (size_t)((M - 1) * a->ld_samples + D)},
                         {a->targets, a->targets ? (size_t)M * 4 : 0},
                         {a->index, (size_t)((N - 1) * a->s_index + S * B) * 4},
@@ -713,17 +856,8 @@ int shape_image_batch(const dl_image_batch_args *a, int n_cus, ImageBatchPlan *o
                        {a->cursor, a->cursor ? (size_t)4 : 0}};
     static const char *const in_name[5] = {"samples", "targets", "index", "aug", "lut"};
     static const char *const out_name[3] = {"data", "labels", "cursor"};
-    for (int i = 0; i < 3; ++i) {
-        if (!o[i].n) continue;
-        for (int j = 0; j < 5; ++j)
-            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
-                return fail(err, DL_ERR_INVALID, "dl_image_batch: %s overlaps %s", out_name[i],
-                            in_name[j]);
-        for (int j = i + 1; j < 3; ++j)
-            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
-                return fail(err, DL_ERR_INVALID, "dl_image_batch: %s overlaps %s", out_name[i],
-                            out_name[j]);
-    }
+    if (const int rc = check_disjoint("dl_image_batch", o, out_name, 3, in, in_name, 5, err))
+        return rc;
     if (!out) return DL_OK;
     ImageBatchPlan &p = *out;
     int sh = 0;
@@ -772,8 +906,97 @@ LenetWs lenet_workspace(int32_t n_agents, int32_t batch, int32_t num_classes) {
     return w;
 }
 
-int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_bytes,
-                LenetPlan *out, char *err) {
+namespace {
+// One operand of a per-agent GEMM: the matrix, its leading dimension, the agent stride and whether
+// it enters transposed.
+struct Mat {
+    const float *p;
+    int64_t ld, stride;
+    int t;
+};
+
+// dl_lenet_grad's launches in order, from the plan's geometry and workspace regions.
+void lenet_steps(const dl_lenet_args &a, char *ws, LenetPlan *out) {
+    LenetPlan &p = *out;
+    const int32_t N = a.n_agents, B = a.batch, nc = a.num_classes;
+    const int F1 = kLenetFc1, F2 = kLenetFc2, P2 = kLenetPool2;
+    const int fc3b = kLenetFc3W + F2 * nc;   // fc3.bias follows fc3.weight [nc][84]
+    auto region = [&](size_t off) { return reinterpret_cast<float *>(ws + off); };
+    float *pool2 = region(p.ws.pool2), *h1 = region(p.ws.h1), *h2 = region(p.ws.h2);
+    float *z = region(p.ws.z), *dz3 = region(p.ws.dz3), *dz2 = region(p.ws.dz2);
+    float *dz1 = region(p.ws.dz1), *da = region(p.ws.da);
+    p.conv = LenetConvArgs{a.X, a.ldx, a.data, a.s_data, region(p.ws.pool1),
+                           reinterpret_cast<uint8_t *>(ws + p.ws.code1), pool2,
+                           reinterpret_cast<uint8_t *>(ws + p.ws.code2), da, region(p.ws.part),
+                           a.G, a.ldg, B, p.train, p.passes, p.fwd_wpa, p.groups, p.bwd_wpa};
+    // the operands: an activation or its gradient [batch][cols] per agent in the workspace; a
+    // weight [rows][cols] at its offset in the parameter row, as stored (x . W) or transposed
+    // (x . W^T: a Linear layer's forward); the same block of the gradient row
+    auto act = [&](float *m, int cols) { return Mat{m, cols, (int64_t)B * cols, 0}; };
+    auto actT = [&](float *m, int cols) { return Mat{m, cols, (int64_t)B * cols, 1}; };
+    auto weight = [&](int off, int cols) { return Mat{a.X + off, cols, a.ldx, 0}; };
+    auto weightT = [&](int off, int cols) { return Mat{a.X + off, cols, a.ldx, 1}; };
+    auto grad = [&](int off, int cols) { return Mat{a.G + off, cols, a.ldg, 0}; };
+    p.n_launches = 0;
+    auto step = [&](int32_t kind) -> LenetStep & {
+        LenetStep &s = p.step[p.n_launches++];
+        s = LenetStep{};
+        s.kind = kind;
+        return s;
+    };
+    // C (M x Nn) = op(A) op(Bm) per agent, then the epilogue
+    auto gemm = [&](int M, int Nn, int K, Mat A, Mat Bm, Mat C, int epi) -> BgemmArgs & {
+        BgemmArgs &g = step(kLenetGemm).gemm;
+        g.batch = N; g.M = M; g.N = Nn; g.K = K;
+        g.A = A.p; g.lda = A.ld; g.sA = A.stride; g.ta = A.t;
+        g.B = Bm.p; g.ldb = Bm.ld; g.sB = Bm.stride; g.tb = Bm.t;
+        g.C = const_cast<float *>(C.p); g.ldc = C.ld; g.sC = C.stride;
+        g.epi = epi;
+        g.sBias = a.ldx;   // a bias is a block of the parameter row, a row sum of the gradient row
+        g.sR = a.ldg;
+        return g;
+    };
+    auto relu_of = [&](BgemmArgs &g, const float *h, int cols) {   // EPI_DRELU's activations
+        g.H = h; g.ldh = cols; g.sH = (int64_t)B * cols;
+    };
+
+    step(kLenetConvFwd);
+    gemm(B, F1, P2, act(pool2, P2), weightT(kLenetFc1W, P2), act(h1, F1), EPI_BIAS_RELU).bias =
+        a.X + kLenetFc1B;
+    gemm(B, F2, F1, act(h1, F1), weightT(kLenetFc2W, F1), act(h2, F2), EPI_BIAS_RELU).bias =
+        a.X + kLenetFc2B;
+    const Mat fc3 = weightT(kLenetFc3W, F2);
+    if (a.logits)
+        gemm(B, nc, F2, act(h2, F2), fc3, Mat{a.logits, a.ldz, a.s_logits, 0}, EPI_BIAS).bias =
+            a.X + fc3b;
+    if (p.head == 1) {
+        BgemmArgs &g = gemm(B, nc, F2, act(h2, F2), fc3, act(dz3, nc), EPI_BIAS_XENT);
+        g.bias = a.X + fc3b;
+        g.labels = a.labels; g.sLab = a.s_labels; g.loss = a.loss;   // dZ3 and the loss in one
+    } else if (p.head == 2) {
+        gemm(B, nc, F2, act(h2, F2), fc3, act(z, nc), EPI_BIAS).bias = a.X + fc3b;
+        step(kLenetHead).head = XentArgs{z, (int64_t)B * nc, a.labels, a.s_labels, dz3,
+                                         (int64_t)B * nc, a.loss, N, B, nc};
+    }
+    if (!p.train) return;
+    // weight gradients dZ^T . (layer input) straight into G, bias gradients as row sums; dZ of
+    // the layer below through the weights, times ReLU's derivative
+    gemm(nc, F2, B, actT(dz3, nc), act(h2, F2), grad(kLenetFc3W, F2), EPI_NONE).rowsum = a.G + fc3b;
+    relu_of(gemm(B, F2, nc, act(dz3, nc), weight(kLenetFc3W, F2), act(dz2, F2), EPI_DRELU), h2, F2);
+    gemm(F2, F1, B, actT(dz2, F2), act(h1, F1), grad(kLenetFc2W, F1), EPI_NONE).rowsum =
+        a.G + kLenetFc2B;
+    relu_of(gemm(B, F1, F2, act(dz2, F2), weight(kLenetFc2W, F1), act(dz1, F1), EPI_DRELU), h1, F1);
+    gemm(F1, P2, B, actT(dz1, F1), act(pool2, P2), grad(kLenetFc1W, P2), EPI_NONE).rowsum =
+        a.G + kLenetFc1B;
+    // the gradient entering the second pooling: dZ1 . fc1.weight
+    gemm(B, P2, F1, act(dz1, F1), weight(kLenetFc1W, P2), act(da, P2), EPI_NONE);
+    step(kLenetConvBwd);
+    step(kLenetConvReduce);
+}
+}  // namespace
+
+int shape_lenet(const dl_lenet_args *a, int n_cus, void *ws, size_t ws_bytes, LenetPlan *out,
+                char *err) {
     if (!a) return fail(err, DL_ERR_INVALID, "dl_lenet_grad: args is NULL");
     const int64_t N = a->n_agents, B = a->batch, nc = a->num_classes;
     if (!a->X || !a->data) return fail(err, DL_ERR_INVALID, "dl_lenet_grad: null X or data");
@@ -818,8 +1041,6 @@ int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_byt
     if (!ws_holds(ws, ws_bytes, w.total))
         return fail(err, DL_ERR_WORKSPACE, "dl_lenet_grad: needs a 16-byte aligned workspace of "
                                            "%zu bytes (dl_lenet_workspace_bytes)", w.total);
-    // no output may share a byte with an input or another output
-    struct Span { const void *p; size_t n; };
     const Span in[3] = {{a->X, (size_t)((N - 1) * a->ldx + P) * 4},
                         {a->data, (size_t)((N - 1) * a->s_data + B * kLenetImage) * 4},
                         {a->labels, a->labels ? (size_t)((N - 1) * a->s_labels + B) * 4 : 0}};
@@ -830,17 +1051,8 @@ int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_byt
                        {ws, w.total}};
     static const char *const in_name[3] = {"X", "data", "labels"};
     static const char *const out_name[4] = {"G", "loss", "logits", "workspace"};
-    for (int i = 0; i < 4; ++i) {
-        if (!o[i].n) continue;
-        for (int j = 0; j < 3; ++j)
-            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
-                return fail(err, DL_ERR_INVALID, "dl_lenet_grad: %s overlaps %s", out_name[i],
-                            in_name[j]);
-        for (int j = i + 1; j < 4; ++j)
-            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
-                return fail(err, DL_ERR_INVALID, "dl_lenet_grad: %s overlaps %s", out_name[i],
-                            out_name[j]);
-    }
+    if (const int rc = check_disjoint("dl_lenet_grad", o, out_name, 4, in, in_name, 3, err))
+        return rc;
     if (!out) return DL_OK;
     LenetPlan &p = *out;
     p.train = a->G ? 1 : 0;
@@ -852,10 +1064,9 @@ int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_byt
     p.bwd_wpa = (int32_t)(want < p.groups ? want : p.groups);
     p.fwd_grid = (int32_t)(N * p.fwd_wpa);   // <= 65535 + 4 * n_cus
     p.bwd_grid = (int32_t)(N * p.bwd_wpa);
-    // conv forward, fc1, fc2, [fc3 -> logits], [fc3 + head: 1 or 2], [5 GEMMs, dA, conv
-    // backward, reduce]
-    p.n_launches = 3 + (a->logits ? 1 : 0) + p.head + (p.train ? 8 : 0);
     p.ws = w;
+    p.n_agents = a->n_agents;
+    lenet_steps(*a, static_cast<char *>(ws), &p);
     return DL_OK;
 }
 
@@ -915,8 +1126,6 @@ int shape_lenet_eval(const dl_lenet_eval_args *a, int n_cus, const void *ws, siz
     if (check_ws && !ws_holds(ws, ws_bytes, w.total))
         return fail(err, DL_ERR_WORKSPACE, "dl_lenet_eval: needs a 16-byte aligned workspace of "
                                            "%zu bytes (dl_lenet_eval_workspace_bytes)", w.total);
-    // no output may share a byte with an input or another output
-    struct Span { const void *p; size_t n; };
     const Span in[3] = {{a->X, (size_t)((N - 1) * a->ldx + P) * 4},
                         {a->data, (size_t)((N - 1) * a->s_data + R * kLenetImage) * 4},
                         {a->labels, a->labels ? (size_t)((N - 1) * a->s_labels + R) * 4 : 0}};
@@ -927,17 +1136,8 @@ int shape_lenet_eval(const dl_lenet_eval_args *a, int n_cus, const void *ws, siz
                        {ws, check_ws ? w.total : 0}};
     static const char *const in_name[3] = {"X", "data", "labels"};
     static const char *const out_name[4] = {"loss", "correct", "logits", "workspace"};
-    for (int i = 0; i < 4; ++i) {
-        if (!o[i].n) continue;
-        for (int j = 0; j < 3; ++j)
-            if (in[j].n && overlaps(o[i].p, o[i].n, in[j].p, in[j].n))
-                return fail(err, DL_ERR_INVALID, "dl_lenet_eval: %s overlaps %s", out_name[i],
-                            in_name[j]);
-        for (int j = i + 1; j < 4; ++j)
-            if (o[j].n && overlaps(o[i].p, o[i].n, o[j].p, o[j].n))
-                return fail(err, DL_ERR_INVALID, "dl_lenet_eval: %s overlaps %s", out_name[i],
-                            out_name[j]);
-    }
+    if (const int rc = check_disjoint("dl_lenet_eval", o, out_name, 4, in, in_name, 3, err))
+        return rc;
     const int32_t blocks = eval_blocks(a->rows);
     int64_t rs = a->row_splits > 0
                      ? a->row_splits

@@ -1,7 +1,12 @@
-// Launch shaping of the gossip rounds: host-only C++17, no HIP, like the planner beside it.  Pure
-// functions of (args, compute units, knobs, workspace pointer and size) that validate a call and
-// describe what it launches -- every kernel's TileArgs, grid, LDS bytes and selectors, and the
-// step after the launches; the C ABI (capi.hip) turns the description into launch_* calls.
+// Launch shaping: host-only C++17, no HIP, like the planner beside it.  Pure functions of (args,
+// compute units, knobs, workspace pointer and size) that validate a call and describe what it
+// launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
+// launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
+// rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round and their plan queries),
+// the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
+// dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
+// functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
+// deviation, the conversions and the step-rows functions.
 #pragma once
 #include "plan.h"
 
@@ -99,10 +104,26 @@ inline bool ws_holds(const void *ws, size_t ws_bytes, size_t need) {
     return ws && aligned16(ws) && ws_bytes >= need;
 }
 
+// The optimizer of dl_sgd_step and the fused momentum round (sgd_elem.h), and the round's momentum
+// buffers: laid out as x, with their FAST-path strides (tile_stride).  buf is read only when mu
+// != 0.
+struct SgdParams {
+    float lr, mu, damp, wd;
+    int first, nesterov;
+};
+struct SgdTileArgs {
+    float *buf;
+    int64_t ldb;
+    int64_t bts;    // FAST-path tile stride in bytes
+    uint32_t brs;   // FAST-path row stride in bytes
+    SgdParams p;
+};
+
 // One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
 // launch_* functions of dl_internal.h take them.
 enum LaunchKind : int32_t {
     kLaunchTile,      // launch_mix_tile(t, chunks, sgd, dev, mix, grid, lds, fast)
+    kLaunchSgdTile,   // launch_mix_sgd_tile(t, q, chunks, dev, grid, lds, fast)
     kLaunchTileReg,   // launch_mix_tile_reg(t, chunks, head, tail_fmt, sgd, dev, grid, lds)
     kLaunchGather,    // launch_mix_gather(t, sgd, columns)
     kLaunchMulti,     // launch_mix_multi(t, chunks, rounds, sgd, dev, grid, lds)
@@ -117,6 +138,7 @@ struct Launch {
     bool columns;              // gather: Knobs::gather_order_columns
     bool planes, gm, narrow;   // traced passes
     TileArgs t;
+    SgdTileArgs q;             // kLaunchSgdTile
 };
 // What follows the launches on the stream.
 enum After : int32_t {
@@ -151,6 +173,13 @@ void tile_stride(bool tiled, int64_t ld, int64_t rows, int64_t T, int64_t *ts, u
 // the float4 kernels out
 int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_t ws_bytes,
                 Launches *out, char *err, bool vec_ok = true);
+// dl_sgd_round / dl_sgd_round_plan, in the header's order: the round's own checks (with y == x
+// allowed) and the momentum buffer's, the plan (refused unless path 1; copied to *plan when
+// given), then shape_round with the float4 kernels ruled out when they cannot reach the buffers,
+// every launch a kLaunchSgdTile with its SgdTileArgs.  out NULL: the plan query, which stops
+// after the plan and needs `plan`.
+int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void *ws,
+                    size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err);
 int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
@@ -175,6 +204,22 @@ constexpr size_t eval_part_bytes(int32_t n_agents, int32_t rows) {
 constexpr size_t eval_workspace_bytes(int32_t n_agents, int32_t rows) {
     return n_agents > 0 && rows > 0 ? 2 * eval_part_bytes(n_agents, rows) : 0;
 }
+// dl_mlp_grad's gate and the split gradient path's workspace (dl_mlp_args.workspace: one
+// activation buffer per agent), from the fused kernels' geometry (mlp_fused.hip asserts each).
+constexpr int kMlpBatch = 64;         // batch rows per agent
+constexpr int kMlpMaxHidden = 152;    // hidden width the five K slices and an LDS row hold
+constexpr int kMlpMaxOutput = 16;
+constexpr int kMlpActStride = 156;    // floats of an activation row in LDS
+constexpr bool mlp_fused_supported(int batch, int din, int dh, int dout) {
+    return batch == kMlpBatch && din > 0 && din % 4 == 0 && dh > 0 && dh <= kMlpMaxHidden &&
+           dh % 2 == 0 && dout > 0 && dout <= kMlpMaxOutput;
+}
+constexpr size_t mlp_workspace_floats(int n_agents) {
+    return (size_t)n_agents * kMlpBatch * kMlpActStride;
+}
+// Every check of dl_mlp_grad (n_agents == 0 passes: the caller launches nothing).
+int shape_mlp_grad(const dl_mlp_args *a, char *err);
+
 // Checks a dl_mlp_eval call and shapes its grid: blocks = ceil(rows / 64); row_splits so that
 // n_agents * row_splits workgroups cover the compute units, at most `blocks`; the caller's hint
 // (args.row_splits > 0) instead, clamped to [1, blocks].  check_ws: the workspace too
@@ -253,8 +298,45 @@ struct ImageBatchPlan {
 // kImageWavesPerCu) waves.
 int shape_image_batch(const dl_image_batch_args *a, int n_cus, ImageBatchPlan *out, char *err);
 
-// dl_lenet_grad: LeNet's fixed geometry, the workspace regions and the grids of the two
-// convolution kernels (lenet.hip).
+// dl_bgemm's kernel parameter (bgemm.hip) and epilogues (DL_EPI_* of dlamd.h).
+enum Epi {
+    EPI_NONE = 0,
+    EPI_BIAS = 1,
+    EPI_BIAS_RELU = 2,
+    EPI_BIAS_TANH = 3,
+    EPI_BIAS_ELU = 4,
+    EPI_DRELU = 5,
+    EPI_DTANH = 6,
+    EPI_DELU = 7,
+    EPI_BIAS_XENT = 8
+};
+struct BgemmArgs {
+    int32_t batch, M, N, K;
+    const float *A;
+    int64_t lda, sA;
+    int32_t ta;
+    const float *B;
+    int64_t ldb, sB;
+    int32_t tb;
+    float *C;
+    int64_t ldc, sC;
+    int32_t epi;
+    const float *bias;
+    int64_t sBias;
+    const float *H;
+    int64_t ldh, sH;
+    float *rowsum;
+    int64_t sR;
+    const int32_t *labels;
+    int64_t sLab;
+    float *loss;
+};
+// Every check of dl_bgemm, and the kernel's parameter of a call that passed.
+int check_bgemm(const dl_bgemm_args *a, char *err);
+BgemmArgs bgemm_args(const dl_bgemm_args &a);
+
+// dl_lenet_grad: LeNet's fixed geometry, the workspace regions, the grids of the two
+// convolution kernels (lenet.hip) and the launches in order.
 constexpr int kLenetImage = 3 * 32 * 32;     // floats of one input image
 constexpr int kLenetPool1 = 6 * 14 * 14;     // relu(conv1) pooled: conv2's input
 constexpr int kLenetPool2 = 16 * 5 * 5;      // relu(conv2) pooled: fc1's input, index c*25 + y*5 + x
@@ -284,6 +366,47 @@ struct LenetWs {
     size_t pool1, code1, pool2, code2, h1, h2, z, dz3, dz2, dz1, da, part, total;
 };
 LenetWs lenet_workspace(int32_t n_agents, int32_t batch, int32_t num_classes);
+// The convolution kernels' parameter.  The workspace pointers are the regions of LenetWs (agent
+// stride batch x the per-image size).
+struct LenetConvArgs {
+    const float *X;          // parameter rows; the 2872 convolution parameters lead each
+    int64_t ldx;
+    const float *data;       // [batch][3][32][32] per agent
+    int64_t s_data;
+    float *pool1;            // [batch][1176]: written by the forward with train, read by the backward
+    uint8_t *code1;          // [batch][1176] winner codes, likewise
+    float *pool2;            // [batch][400]: fc1's input, always written
+    uint8_t *code2;          // [batch][400]
+    const float *da;         // [batch][400]: d loss / d pool2 (backward)
+    float *part;             // [groups][2872] per agent: the backward's group partials
+    float *G;                // the reduce's destination
+    int64_t ldg;
+    int32_t batch, train;
+    int32_t passes, fwd_wpa, groups, bwd_wpa;
+};
+// The stand-alone cross-entropy head (launch_xent_grad's arguments).
+struct XentArgs {
+    const float *Z;
+    int64_t sZ;
+    const int32_t *y;
+    int64_t sY;
+    float *dZ;
+    int64_t sD;
+    float *loss;
+    int32_t batch, rows, classes;
+};
+enum LenetStepKind : int32_t {
+    kLenetConvFwd,      // launch_lenet_conv_fwd(conv, fwd_grid)
+    kLenetGemm,         // launch_bgemm(gemm)
+    kLenetHead,         // launch_xent_grad(head ...)
+    kLenetConvBwd,      // launch_lenet_conv_bwd(conv, bwd_grid)
+    kLenetConvReduce,   // launch_lenet_conv_reduce(conv, n_agents)
+};
+struct LenetStep {
+    int32_t kind;
+    BgemmArgs gemm;   // kLenetGemm
+    XentArgs head;    // kLenetHead
+};
 struct LenetPlan {
     int32_t train;                // G given: the backward runs
     int32_t head;                 // 0: no loss (logits only), 1: fused into fc3's GEMM, 2: fc3 +
@@ -292,13 +415,16 @@ struct LenetPlan {
                                   // workgroup w of an agent walks passes w, w + fwd_wpa, ...
     int32_t groups, bwd_wpa;      // backward: ceil(batch / kLenetGroup) groups, walked likewise
     int32_t fwd_grid, bwd_grid;   // n_agents * wpa workgroups of kLenetThreads
-    int32_t n_launches;
     LenetWs ws;
+    LenetConvArgs conv;           // the convolution steps' parameter
+    int32_t n_agents;
+    int32_t n_launches;           // the steps: what dl_lenet_grad launches, in order
+    LenetStep step[kLenetMaxLaunches];
 };
 // Checks a dl_lenet_grad call and shapes it.  Either kernel runs wpa = ceil(kLenetWgPerCu *
 // n_cus / n_agents) workgroups per agent, at least 1 and at most the agent's passes / groups.
-int shape_lenet(const dl_lenet_args *a, int n_cus, const void *ws, size_t ws_bytes,
-                LenetPlan *out, char *err);
+int shape_lenet(const dl_lenet_args *a, int n_cus, void *ws, size_t ws_bytes, LenetPlan *out,
+                char *err);
 
 // dl_lenet_eval: blocks of kEvalBlockRows rows as dl_mlp_eval's, the LDS of one workgroup
 // (lenet_eval.hip asserts it: two workgroups a compute unit), and the workspace: [n_agents]

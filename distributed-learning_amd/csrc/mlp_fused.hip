@@ -1809,12 +1809,12 @@ __global__ void __launch_bounds__(256) mlp_eval_reduce_kernel(const float *part,
 
 }  // namespace
 
-int mlp_fused_supported(int batch, int din, int dh, int dout) {
-    return batch == MB && din > 0 && din % 4 == 0 && dh > 0 && dh <= 152 && dh % 2 == 0 && dout > 0 &&
-           dout <= 16;
-}
-
-size_t mlp_workspace_floats(int n_agents) { return (size_t)n_agents * H_FLOATS; }
+// launch.h states the gate (mlp_fused_supported) and the split path's workspace of one activation
+// buffer per agent (mlp_workspace_floats) from these
+static_assert(MB == kMlpBatch && LDH == kMlpActStride && H_FLOATS == kMlpBatch * kMlpActStride,
+              "launch.h states this file's batch and activation stride");
+static_assert(kMlpMaxHidden <= NSL * BK && kMlpMaxHidden + 4 <= LDH && kMlpMaxOutput == 16,
+              "launch.h states this file's hidden and output limits");
 
 hipError_t launch_mlp_fused(const float *X, int64_t ldx, const float *data, int64_t s_data,
                             const int32_t *labels, int64_t s_lab, float *G, int64_t ldg,

@@ -9,12 +9,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace dl {
+#include "launch.h"   // SgdParams
 
-struct SgdParams {
-    float lr, mu, damp, wd;
-    int first, nesterov;
-};
+namespace dl {
 
 __device__ __forceinline__ float sgd_elem(float x, float g, float &b, const SgdParams &p) {
     float d = p.wd != 0.f ? __builtin_fmaf(p.wd, x, g) : g;

@@ -1,7 +1,8 @@
 // The launch shaping alone (csrc/launch.cpp + plan.cpp, no HIP, no library): replays
 // tests/golden/mix_launches.txt (format: test_launch_sweep_cpu.py) through the pure functions at
 // 256 compute units, compares every launch, follow-up and refusal with the line, and checks what
-// must hold of any launch list.  Built with the address and undefined-behaviour sanitizers by
+// must hold of any launch list; a momentum round's plan query (shape_sgd_round without a launch
+// list) must refuse what the round refuses.  Built with the address and undefined-behaviour sanitizers by
 // test_launch_sweep_cpu.py.
 #include <fstream>
 #include <iostream>
@@ -49,6 +50,8 @@ std::string fmt(const dl::Launch &l) {
     switch (l.kind) {
         case dl::kLaunchTile:
             return fmt_launch("tile", {l.chunks, l.sgd, l.dev, l.mix, l.fast, l.grid, l.lds}, l.t);
+        case dl::kLaunchSgdTile:
+            return fmt_sgd_launch(l.chunks, l.dev, l.fast, l.grid, l.lds, l.t, l.q);
         case dl::kLaunchTileReg:
             return fmt_launch("reg", {l.chunks, l.head, l.tail_fmt, l.sgd, l.dev, l.grid, l.lds},
                               l.t);
@@ -121,7 +124,7 @@ void check_launches(const Case &c, const dl::Launches &L) {
 
 int main(int argc, char **argv) {
     std::ifstream in(argc > 1 ? argv[1] : "tests/golden/mix_launches.txt");
-    const int floor = 630;   // the lines of the committed table
+    const int floor = 792;   // the lines of the committed table
     std::string line;
     int n = 0;
     for (; std::getline(in, line); ++n) {
@@ -142,6 +145,29 @@ int main(int argc, char **argv) {
                 if (c.entry == "dev") rc = DL_OK, L.after = dl::kAfterTwoPass;
                 else snprintf(err, sizeof err, "dl_deviation_tiled: %d rows exceed one tile",
                               a.W.n_rows);
+            }
+        } else if (c.entry == "sgdround") {
+            const dl_sgd_round_args q = c.sgd();
+            rc = dl::shape_sgd_round(c.null_args ? nullptr : &q, 256, k, c.ws, c.ws_bytes, nullptr,
+                                     &L, err);
+            // the plan query: the same refusal, or the plan of a call that is shaped (and of one
+            // that only the workspace or the launch list stops)
+            char perr[dl::kErrLen] = "";
+            dl_mix_plan pub{};
+            const int prc = dl::shape_sgd_round(c.null_args ? nullptr : &q, 256, k, nullptr, 0, &pub,
+                                                nullptr, perr);
+            if (rc == 0) {
+                EXPECT(prc == 0 && pub.path == 1);
+                for (int i = 0; i < L.n; ++i) {
+                    const dl::Launch &l = L.l[i];
+                    EXPECT(l.kind == dl::kLaunchSgdTile && l.sgd && l.mix);
+                    EXPECT(l.q.p.lr == a.lr && (l.q.buf != nullptr) == (q.momentum != 0.f));
+                }
+            } else if (prc) {
+                EXPECT(prc == rc && std::string(perr) == err);
+            } else {
+                EXPECT(rc == DL_ERR_WORKSPACE || std::string(err).find("tiled operands") !=
+                                                     std::string::npos);
             }
         } else {
             rc = dl::check_mix_args(c.null_args ? nullptr : &a, err);

@@ -10,11 +10,12 @@ A line reads
     n_params tile_cols n_halo n_local_src deviation lagged ldx ldy ldg ldh misalignment
     halo_blocks n_hub_rows ws_misalignment ws_bytes rounds flags knob -> status result
 with entry one of round (dl_mix_round), rounds (dl_mix_rounds), trace (dl_mix_rounds_trace), dev
-(dl_deviation) and devtiled (dl_deviation_tiled); misalignment the bytes x:y:g:halo are off their
-16-byte aligned addresses; halo_blocks 0 or n:rows:rows:...; ws_bytes -1 for a null workspace;
+(dl_deviation), devtiled (dl_deviation_tiled) and sgdround (dl_sgd_round); misalignment the bytes
+x:y:g:halo[:buf] are off their 16-byte aligned addresses; halo_blocks 0 or n:rows:rows:...; ws_bytes -1 for a null workspace;
 flags `-` or a comma list (launch_table.h: g, mean, nodevsq, pro, nullx, y=x, ...); knob `-` or
 NAME=value.  The result is the error text, or the launches and then `; follow-up`:
     tile chunks sgd dev mix fast grid lds {TileArgs}
+    sgdtile chunks dev fast grid lds {TileArgs} {buf ldb bts brs lr mu damp wd first nesterov}
     reg chunks head tail_fmt sgd dev grid lds {TileArgs}
     gather sgd columns {TileArgs}
     multi chunks rounds sgd dev grid lds {TileArgs}
@@ -26,7 +27,10 @@ operand's address or `-`, the halo block tables up to n_hblk.
 
 The right sides were recorded from the commit before launch shaping moved out of capi.hip: that
 commit's capi.hip and plan.cpp linked against recording stubs of the dl::launch_* functions, run
-on the CPU over these left sides."""
+on the CPU over these left sides.  The sgdround lines (flags mu=, ldb=, damp=, wd=, nest, first,
+nullbuf, buf=x|y|g for the momentum buffer and the optimizer) were recorded the same way from the
+commit before dl_sgd_round's shaping moved: that commit's capi.hip, plan.cpp and launch.cpp against
+recording stubs of launch_mix_sgd_tile, launch_dev_reduce and hipMemsetAsync."""
 import os
 import shutil
 import subprocess

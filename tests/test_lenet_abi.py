@@ -3,8 +3,25 @@ are additive (ABI still 10), the parameter count and ``BatchedLeNet.offsets`` ar
 table and the ``LeNet`` module's, the workspace grows with each argument, every refusal the
 header states comes back with its status and its own message before any device call (dummy
 pointers, runs without a GPU), and the host-only shaping (csrc/launch.cpp shape_lenet) walks
-every pass and group once inside a disjoint workspace -- the latter from tests/lenet_sweep.cpp,
-built with the address and undefined-behaviour sanitizers and run as an ordinary process."""
+every pass and group once inside a disjoint workspace, lists steps whose operands an earlier
+step wrote and whose outputs stay inside their regions, and launches what
+tests/golden/lenet_launches.txt pins -- the latter from tests/lenet_sweep.cpp, built with the
+address and undefined-behaviour sanitizers and run as an ordinary process.
+
+A line of the table reads
+    name n_agents batch num_classes ldx_pad ldg_pad flags -> status n_launches steps
+with ldx and ldg the parameter count rounded up to 4 plus the pad, ldz = num_classes + 2, s_logits
+= batch * ldz + 5, s_data = batch * 3072, s_labels = batch + 1, and flags a comma list of g (G
+given), loss, logits, nolabels, sdata0 and slab0 (a shared stride of 0).  The steps are, each after
+the event e<k> recorded before it and the last followed by one more event,
+    fwd grid {LenetConvArgs} | gemm {BgemmArgs} | head {launch_xent_grad's arguments} |
+    bwd grid {LenetConvArgs} | reduce n_agents {LenetConvArgs}
+with every field in declaration order and a pointer as its operand's name plus the byte offset
+(X, DATA, LABELS, G, LOSS, LOGITS, WS).  The right sides were recorded at 256 compute units from
+the commit before the step list: that commit's capi.hip, plan.cpp and launch.cpp linked against
+recording stubs of launch_bgemm, launch_xent_grad, the three launch_lenet_conv_* functions and
+hipEventRecord, run on the CPU over these left sides through dl_lenet_grad_events (and through
+dl_lenet_grad, which launched the same without the events)."""
 import ctypes
 import os
 import shutil
@@ -212,6 +229,8 @@ def test_sanitized_lenet_sweep(tmp_path):
                     os.path.join(ROOT, "tests", "lenet_sweep.cpp"),
                     os.path.join(CSRC, "launch.cpp"), os.path.join(CSRC, "plan.cpp"),
                     "-o", exe], check=True)
-    run = subprocess.run([exe], capture_output=True, text=True)
+    run = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "lenet_launches.txt")],
+                         capture_output=True, text=True)
     assert run.returncode == 0 and not run.stderr, run.stdout + run.stderr[:4000]
-    assert run.stdout.split() == ["180", "calls,", "0", "failures"]
+    # 180 calls of the grid and the 72 lines of the table
+    assert run.stdout.split() == ["252", "calls,", "0", "failures"]

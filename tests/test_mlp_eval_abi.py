@@ -1,9 +1,13 @@
 """CPU checks of the evaluation entry's C ABI (dl_mlp_eval, dl_mlp_eval_plan_query,
 dl_mlp_eval_workspace_bytes): the struct layouts agree between C and ctypes, the grid shaping
 follows the header's rule, and every refusal the header states comes back with its status and
-message before any device call (dummy pointers, runs without a GPU)."""
+message before any device call (dummy pointers, runs without a GPU).  Also dl_mlp_grad's and
+dl_bgemm's checks on their own (csrc/launch.cpp shape_mlp_grad, check_bgemm) from
+tests/mlp_sweep.cpp, built with the address and undefined-behaviour sanitizers and run as an
+ordinary process."""
 import ctypes
 import os
+import shutil
 import subprocess
 
 import pytest
@@ -192,3 +196,19 @@ def test_workspace_refusals():
     # argument refusals come first, whatever the workspace
     assert lib.dl_mlp_eval(ctypes.byref(valid(hidden_dim=151)), None, 0, None) == \
         _lib.DL_ERR_UNSUPPORTED
+
+
+def test_sanitized_mlp_sweep(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("clang++", path="/opt/rocm/llvm/bin")
+    if not cxx:
+        pytest.skip("no host C++ compiler (g++ or the ROCm clang++)")
+    csrc = os.path.join(ROOT, "distributed-learning_amd", "csrc")
+    exe = str(tmp_path / "mlp_sweep")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc,
+                    os.path.join(ROOT, "tests", "mlp_sweep.cpp"),
+                    os.path.join(csrc, "launch.cpp"), os.path.join(csrc, "plan.cpp"),
+                    "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr, run.stdout + run.stderr[:4000]
+    assert run.stdout.split() == ["91", "calls,", "0", "failures"]
