@@ -98,6 +98,10 @@ class DlSgdRoundArgs(ctypes.Structure):
                 ("dampening", _f32), ("weight_decay", _f32), ("nesterov", _i32), ("first", _i32)]
 
 
+class DlChebRoundArgs(ctypes.Structure):
+    _fields_ = [("mix", DlMixArgs), ("z", _vp), ("ldz", _i64), ("a", _f32), ("b", _f32)]
+
+
 class DlMlpArgs(ctypes.Structure):
     _fields_ = [("n_agents", _i32), ("batch", _i32), ("input_dim", _i32), ("hidden_dim", _i32),
                 ("output_dim", _i32), ("X", _vp), ("ldx", _i64), ("data", _vp), ("s_data", _i64),
@@ -193,6 +197,9 @@ SIGNATURES = {
     "dl_sgd_step": (_i32, [ctypes.POINTER(DlSgdArgs), _vp]),
     "dl_sgd_round_plan": (_i32, [ctypes.POINTER(DlSgdRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_sgd_round": (_i32, [ctypes.POINTER(DlSgdRoundArgs), _vp, _sz, _vp]),
+    "dl_cheb_round_plan": (_i32, [ctypes.POINTER(DlChebRoundArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_cheb_round": (_i32, [ctypes.POINTER(DlChebRoundArgs), _vp, _sz, _vp]),
+    "dl_axpby": (_i32, [_vp, _i64, _vp, _i64, _f32, _f32, _vp, _i64, _i32, _i64, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),
     "dl_mlp_eval_workspace_bytes": (_sz, [_i32, _i32]),

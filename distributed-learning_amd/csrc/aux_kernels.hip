@@ -215,6 +215,32 @@ __global__ void __launch_bounds__(256) sgd_step_kernel(const float *x, int64_t l
     }
 }
 
+// out = fl(fl(a s) + fl(b z)) over a block of agent rows: the Chebyshev round's second line
+// (mix_cheb.hip axpby4; -ffp-contract=off keeps the three operations apart), as a launch of its
+// own behind dl_mix_round.  out may alias s or z: a thread reads an element before it writes it.
+// VEC: float4 accesses over the first n_params / 4 chunks of a row, then the scalar tail.
+template <bool VEC>
+__global__ void __launch_bounds__(256) axpby_kernel(const float *s, int64_t lds_, const float *z,
+                                                    int64_t ldz, float a, float b, float *out,
+                                                    int64_t ldo, int64_t n_params) {
+    const int r = blockIdx.y;
+    const float *sr = s + (int64_t)r * lds_;
+    const float *zr = z + (int64_t)r * ldz;
+    float *orow = out + (int64_t)r * ldo;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t n4 = VEC ? n_params >> 2 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const v4f sv = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(sr) + i);
+        const v4f zv = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(zr) + i);
+        v4f ov;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ov[k] = a * sv[k] + b * zv[k];
+        reinterpret_cast<v4f *>(orow)[i] = ov;
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_params; i += stride)
+        orow[i] = a * sr[i] + b * zr[i];
+}
+
 // ---------------------------------------------------------------- Perron / asyncio round
 // One Jacobi iteration on element i of an [R, TP] tile held in LDS (cur), neighbour sums in
 // socket order (np.sum(list, axis=0): first term, then left fold), then scale.
@@ -445,6 +471,24 @@ hipError_t launch_sgd_step(const float *x, int64_t ldx, const float *g, int64_t 
     else
         hipLaunchKernelGGL(sgd_step_kernel<false>, dim3((unsigned)bx, n_rows), dim3(256), 0, s, x,
                            ldx, g, ldg, buf, ldb, out, ldo, n_params, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_axpby(const float *src, int64_t lds_, const float *z, int64_t ldz, float a,
+                        float b, float *out, int64_t ldo, int n_rows, int64_t n_params, bool vec,
+                        hipStream_t s) {
+    const int64_t work = vec ? (n_params + 3) >> 2 : n_params;
+    int64_t bx = (work + 255) / 256;
+    // ~16 workgroups per CU over all rows, each thread a few float4s (grid-stride)
+    int64_t cap = (8192 + n_rows - 1) / n_rows;
+    if (cap < 1) cap = 1;
+    if (bx > cap) bx = cap;
+    if (vec)
+        hipLaunchKernelGGL(axpby_kernel<true>, dim3((unsigned)bx, n_rows), dim3(256), 0, s, src,
+                           lds_, z, ldz, a, b, out, ldo, n_params);
+    else
+        hipLaunchKernelGGL(axpby_kernel<false>, dim3((unsigned)bx, n_rows), dim3(256), 0, s, src,
+                           lds_, z, ldz, a, b, out, ldo, n_params);
     return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 // the environment knobs, read once per call.  What an entry point checks and launches is decided
 // by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here their
 // description of a call is turned into launch_* calls and the step after them.  Shaped there:
-// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round), the one-pass
+// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round), the one-pass
 // deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch, dl_lenet_grad
 // and dl_lenet_eval.  The others (dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
 // deviation, the conversions, the step-rows functions, ...) check their own arguments here:
@@ -137,6 +137,9 @@ int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, cons
                 break;
             case dl::kLaunchSgdTile:
                 e = dl::launch_mix_sgd_tile(l.t, l.q, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
+                break;
+            case dl::kLaunchChebTile:
+                e = dl::launch_mix_cheb_tile(l.t, l.c, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
                 break;
             case dl::kLaunchTileReg:
                 e = dl::launch_mix_tile_reg(l.t, l.chunks, l.head, l.tail_fmt, l.sgd, l.dev, l.grid,
@@ -686,6 +689,46 @@ int dl_sgd_round(const dl_sgd_round_args *args, void *workspace, size_t ws_bytes
     if (rc) return status(rc, err);
     return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, "mix_sgd_tile_kernel",
                static_cast<hipStream_t>(stream));
+}
+
+int dl_cheb_round_plan(const dl_cheb_round_args *args, dl_mix_plan *plan) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    return status(dl::shape_cheb_round(args, device_cus(), dl::read_knobs(), nullptr, 0, plan,
+                                       nullptr, err), err);
+}
+
+int dl_cheb_round(const dl_cheb_round_args *args, void *workspace, size_t ws_bytes,
+                  dl_stream_t stream) {
+    g_err.clear();
+    dl::Launches L;
+    char err[dl::kErrLen];
+    const int rc = dl::shape_cheb_round(args, device_cus(), dl::read_knobs(), workspace, ws_bytes,
+                                        nullptr, &L, err);
+    if (rc) return status(rc, err);
+    return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, "mix_cheb_tile_kernel",
+               static_cast<hipStream_t>(stream));
+}
+
+int dl_axpby(const float *s, int64_t lds_, const float *z, int64_t ldz, float a, float b,
+             float *out, int64_t ldo, int32_t n_rows, int64_t n_params, dl_stream_t stream) {
+    g_err.clear();
+    if (n_rows == 0 || n_params == 0) return DL_OK;
+    if (!s || !z || !out || n_rows < 0 || n_rows > 65535 || n_params < 0 || lds_ < n_params ||
+        ldz < n_params || ldo < n_params)
+        return fail(DL_ERR_INVALID, "dl_axpby: bad arguments (n_rows %d, n_params %lld)", n_rows,
+                    (long long)n_params);
+    const size_t rb = (size_t)n_params * sizeof(float);
+    auto extent = [&](int64_t ld) { return ((size_t)n_rows - 1) * ld * 4 + rb; };
+    if (!(out == s && ldo == lds_) && overlaps(out, extent(ldo), s, extent(lds_)))
+        return fail(DL_ERR_INVALID, "dl_axpby: out must be s itself or not overlap it");
+    if (!(out == z && ldo == ldz) && overlaps(out, extent(ldo), z, extent(ldz)))
+        return fail(DL_ERR_INVALID, "dl_axpby: out must be z itself or not overlap it");
+    const bool vec = aligned16(s) && aligned16(z) && aligned16(out) && (lds_ & 3) == 0 &&
+                     (ldz & 3) == 0 && (ldo & 3) == 0;
+    hipError_t e = dl::launch_axpby(s, lds_, z, ldz, a, b, out, ldo, n_rows, n_params, vec,
+                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DL_OK : hip_fail(e, "axpby launch");
 }
 
 size_t dl_mlp_workspace_bytes(int32_t n_agents) {

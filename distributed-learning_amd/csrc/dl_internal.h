@@ -36,6 +36,15 @@ hipError_t launch_mix_tile_reg(const TileArgs &a, int chunks, int head, int tail
 // set), plus the momentum buffers and the optimizer's parameters (launch.h SgdTileArgs).
 hipError_t launch_mix_sgd_tile(const TileArgs &a, const SgdTileArgs &q, int chunks, bool dev,
                                int grid, int lds_bytes, bool fast, hipStream_t s);
+// The Chebyshev round's tile kernel (mix_cheb.hip) for one launch of a path-1 round shaped by
+// shape_cheb_round: TileArgs as for launch_mix_tile (no g, no halo rows, no row set), plus z and
+// the coefficients (launch.h ChebTileArgs).
+hipError_t launch_mix_cheb_tile(const TileArgs &a, const ChebTileArgs &q, int chunks, bool dev,
+                                int grid, int lds_bytes, bool fast, hipStream_t s);
+// out = fl(fl(a * s) + fl(b * z)) over n_rows x n_params (aux_kernels.hip); vec: float4 accesses
+hipError_t launch_axpby(const float *src, int64_t lds_, const float *z, int64_t ldz, float a,
+                        float b, float *out, int64_t ldo, int n_rows, int64_t n_params, bool vec,
+                        hipStream_t s);
 // K rounds of mixing on LDS-resident tiles (mix_multi.hip); FAST tiles only, no halo rows
 hipError_t launch_mix_multi(const TileArgs &a, int chunks, int rounds, bool sgd, bool dev,
                             int grid, int lds, hipStream_t s);

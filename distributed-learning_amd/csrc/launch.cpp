@@ -458,6 +458,73 @@ int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void 
     return DL_OK;
 }
 
+int shape_cheb_round(const dl_cheb_round_args *a, int n_cus, const Knobs &k, void *ws,
+                     size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    // the Chebyshev round's own checks around the round's (y == x allowed, y == z below)
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_cheb_round: args is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y || !a->z) return fail(err, DL_ERR_INVALID, "dl_cheb_round: null x/y/z");
+    if (m.g)
+        return fail(err, DL_ERR_INVALID, "dl_cheb_round: g must be NULL (no local step inside the "
+                                         "accelerated round)");
+    if (m.halo || m.n_halo != 0 || m.mean_prev || m.colsum_out || m.n_local_src != 0 ||
+        m.n_halo_blocks != 0 || m.partial_rows_out)
+        return fail(err, DL_ERR_UNSUPPORTED,
+                    "dl_cheb_round: no halo rows, partition row sets or lagged deviation (halo, "
+                    "n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks, partial_rows_out "
+                    "must be NULL / 0)");
+    int rc = check_mix_args(&m, err, true);
+    if (rc) return rc;
+    const bool tiled = m.tile_cols > 0;
+    const int64_t n = m.W.n_rows;
+    if (tiled ? a->ldz < 0 || (a->ldz > 0 && a->ldz < n) || a->ldz > 65535 * 4
+              : a->ldz < m.n_params)
+        return fail(err, DL_ERR_INVALID, "dl_cheb_round: z laid out as x (row-major ldz >= "
+                                         "n_params; column-tiled ldz 0 or >= n_rows)");
+    {
+        const int64_t Tc = m.tile_cols;
+        const int64_t ntl = tiled ? (m.n_params + Tc - 1) / Tc : 0;
+        auto extent = [&](int64_t ld) {
+            return tiled ? (size_t)(((ntl - 1) * (ld ? ld : n) + n) * Tc * 4)
+                         : ((size_t)(n - 1) * ld + m.n_params) * 4;
+        };
+        const bool y_is_z = m.y == a->z && m.ldy == a->ldz;
+        if (!y_is_z && overlaps(a->z, extent(a->ldz), m.y, extent(m.ldy)))
+            return fail(err, DL_ERR_INVALID, "dl_cheb_round: y overlaps z (y may be z itself "
+                                             "with ldy == ldz)");
+    }
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_cheb_round_plan: plan is NULL");
+    Plan pl;
+    rc = plan_mix(m, n_cus, k, &pl, err);
+    if (rc) return rc;
+    if (pl.pub.path != 1)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_round: the fused Chebyshev round runs on the "
+                                             "LDS tile kernel (plan path 1); this round plans "
+                                             "path %d", pl.pub.path);
+    if (plan) *plan = pl.pub;
+    if (!out) return DL_OK;
+    // do the float4 kernels reach z: 16-byte aligned, and row-major rows too, within the 32-bit
+    // offsets of a tile base (as tile_args asks of x and y)
+    const bool z_vec = aligned16(a->z) &&
+                       (tiled || (a->ldz % 4 == 0 &&
+                                  ((n - 1) * a->ldz + 128) * 4 < ((int64_t)1 << 32)));
+    rc = shape_round(m, n_cus, k, ws, ws_bytes, out, err, z_vec);
+    if (rc) return rc;
+    for (int i = 0; i < out->n; ++i) {
+        Launch &l = out->l[i];
+        if (l.kind != kLaunchTile)
+            return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_round: the fused Chebyshev round runs on "
+                                                 "the LDS tile kernel (plan path 1) only");
+        l.kind = kLaunchChebTile;
+        l.c.z = a->z;
+        l.c.ldz = a->ldz;
+        l.c.a = a->a;
+        l.c.b = a->b;
+        tile_stride(l.t.tiled, a->ldz, l.t.n_rows, 4 * l.chunks, &l.c.zts, &l.c.zrs);
+    }
+    return DL_OK;
+}
+
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err) {
     reset(out);

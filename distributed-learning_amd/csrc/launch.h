@@ -2,7 +2,8 @@
 // compute units, knobs, workspace pointer and size) that validate a call and describe what it
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
-// rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round and their plan queries),
+// rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round and their
+// plan queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -119,6 +120,16 @@ struct SgdTileArgs {
     SgdParams p;
 };
 
+// The Chebyshev round's second operand (mix_cheb.hip): z laid out as x, with its FAST-path
+// strides (tile_stride), and the two coefficients of y = fl(fl(a * W x) + fl(b * z)).
+struct ChebTileArgs {
+    const float *z;
+    int64_t ldz;
+    int64_t zts;    // FAST-path tile stride in bytes
+    uint32_t zrs;   // FAST-path row stride in bytes
+    float a, b;
+};
+
 // One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
 // launch_* functions of dl_internal.h take them.
 enum LaunchKind : int32_t {
@@ -129,6 +140,7 @@ enum LaunchKind : int32_t {
     kLaunchMulti,     // launch_mix_multi(t, chunks, rounds, sgd, dev, grid, lds)
     kLaunchTrace,     // launch_mix_trace(t, chunks, planes, rounds, grid, lds, trace): + its reduce
     kLaunchTraceIrr,  // launch_mix_trace_irr(t, head, gm, narrow, rounds, grid, lds, trace): same
+    kLaunchChebTile,  // launch_mix_cheb_tile(t, c, chunks, dev, grid, lds, fast)
 };
 struct Launch {
     int32_t kind;
@@ -139,6 +151,7 @@ struct Launch {
     bool planes, gm, narrow;   // traced passes
     TileArgs t;
     SgdTileArgs q;             // kLaunchSgdTile
+    ChebTileArgs c;            // kLaunchChebTile
 };
 // What follows the launches on the stream.
 enum After : int32_t {
@@ -180,6 +193,13 @@ int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_
 // after the plan and needs `plan`.
 int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void *ws,
                     size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
+// dl_cheb_round / dl_cheb_round_plan, in the header's order: the Chebyshev round's own checks (g
+// refused, y == x and y == z allowed) around the round's, z's strides, the plan (refused unless
+// path 1; copied to *plan when given), then shape_round with the float4 kernels ruled out when
+// they cannot reach z, every launch a kLaunchChebTile with its ChebTileArgs.  out NULL: the plan
+// query, which stops after the plan and needs `plan`.
+int shape_cheb_round(const dl_cheb_round_args *a, int n_cus, const Knobs &k, void *ws,
+                     size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err);
 int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,

@@ -325,6 +325,70 @@ def sgd_round(W: DeviceCsr, X, Y, G, M, lr, momentum=0.0, dampening=0.0, weight_
     return True
 
 
+def _cheb_round_args(W, X, Y, Z, a, b, dev_sq, dev_max, mean, tiled):
+    if W.n_src != W.n_rows or W.n_local != W.n_rows:
+        raise ValueError("cheb_round mixes whole rounds only (no halo rows, no partition row set)")
+    if Z is None:
+        raise ValueError("cheb_round needs the previous iterate Z")
+    if tiled is not None:
+        mix = mix_args_tiled(W, tiled[0], tiled[1], X, Y, None, 0.0, dev_sq, dev_max, mean)
+        ldz = _tiled_ld(Z, "Z", W.n_rows, tiled[0], tiled[1], W.device)
+    else:
+        mix = mix_args(W, X, Y, None, 0.0, None, dev_sq, dev_max, mean)
+        _check(Z, "Z", W.n_rows, X.shape[1], W.device)
+        ldz = _ld(Z)
+    return _lib.DlChebRoundArgs(mix, _lib.ptr(Z), ldz, float(a), float(b))
+
+
+def cheb_round_plan(W: DeviceCsr, X, Y, Z, deviation=False, tiled=None):
+    """dl_cheb_round_plan: the configuration ``cheb_round`` would run for these operands, or None
+    when the fused Chebyshev round does not take them (a plan path other than 1)."""
+    lib = _lib.load()
+    dummy = torch.empty(1, dtype=torch.float32, device=W.device) if deviation else None
+    args = _cheb_round_args(W, X, Y, Z, 1.0, 0.0, dummy, dummy, None, tiled)
+    plan = _lib.DlMixPlan()
+    rc = lib.dl_cheb_round_plan(ctypes.byref(args), ctypes.byref(plan))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "dl_cheb_round_plan")
+    return {f: getattr(plan, f) for f, _ in plan._fields_}
+
+
+def cheb_round(W: DeviceCsr, X, Y, Z, a, b, dev_sq=None, dev_max=None, mean=None,
+               workspace: Workspace = None, tiled=None):
+    """One round of Chebyshev-accelerated gossip on the current stream (dl_cheb_round):
+    Y = fl(fl(a * (W X)) + fl(b * Z)) [+ deviation of Y], W X folded as ``mix_round`` folds it --
+    bit for bit ``mix_round`` into a scratch followed by ``axpby``, in one pass over HBM.  Y may be
+    Z itself (the intended mode: X = x_k, Z = x_{k-1}, the round overwrites the older iterate) or
+    X itself.  ``tiled=(n_params, tile_cols)``: X, Z, Y in the column-tiled layout.  Returns
+    False, launching nothing, when the fused kernel does not take this round (the caller then
+    runs the two launches)."""
+    lib = _lib.load()
+    P = tiled[0] if tiled is not None else X.shape[1]
+    args = _cheb_round_args(W, X, Y, Z, a, b, dev_sq, dev_max, mean, tiled)
+    workspace = workspace or Workspace(W.device)
+    wp, wn = workspace.ptr_size(lib.dl_mix_workspace_bytes(W.n_rows, 0, P))
+    rc = lib.dl_cheb_round(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc, "dl_cheb_round")
+    return True
+
+
+def axpby(S, Z, a, b, out=None):
+    """dl_axpby: out = fl(fl(a * S) + fl(b * Z)) over row-major [n, P] tensors (the Chebyshev
+    round's second line as a launch of its own).  out may be S or Z; default a new tensor."""
+    n, P = S.shape
+    out = torch.empty(n, P, dtype=torch.float32, device=S.device) if out is None else out
+    _check(S, "S", n, P, S.device)
+    _check(Z, "Z", n, P, S.device)
+    _check(out, "out", n, P, S.device)
+    _lib.check(_lib.load().dl_axpby(_lib.ptr(S), _ld(S), _lib.ptr(Z), _ld(Z), float(a), float(b),
+                                    _lib.ptr(out), _ld(out), n, P, _lib.stream_handle(S.device)),
+               "dl_axpby")
+    return out
+
+
 def trace_max_rounds(W: DeviceCsr, X, Y, tiled=None):
     """dl_mix_trace_plan: the most rounds one traced pass can run, or 0 when the traced kernel
     does not fit this graph/layout (then the caller loops ``mix_round``)."""
@@ -825,6 +889,78 @@ class GossipEngine:
                  lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                  nesterov=nesterov, first=first)
         self.round(src=self._S, deviation=deviation, mean=mean)
+
+    def round_cheb(self, a, b, deviation=False, mean=None):
+        """One round of Chebyshev-accelerated gossip: X <- a W X + b X_prev, where X_prev is the
+        iterate before the last round -- what the ping-pong left in ``Y`` -- and is overwritten
+        in place (``cheb_round`` with z = y = Y), so the loop needs no third matrix.  Where the
+        fused kernel does not take the round (plan paths 2, 4, 5) it runs as the plain round into
+        a scratch matrix and ``axpby`` into Y: the same bits, the deviation then from a pass of
+        its own."""
+        tiled = (self.P, self.T) if self.layout == "tiled" else None
+        if cheb_round(self.W, self.X, self.Y, self.Y, a, b,
+                      dev_sq=self.dev_sq if deviation else None,
+                      dev_max=self.dev_max if deviation else None, mean=mean, workspace=self.ws,
+                      tiled=tiled):
+            self.X, self.Y = self.Y, self.X
+            return
+        if getattr(self, "_S", None) is None:
+            self._S = self._empty()
+        mix_round(self.W, self.X, self._S, workspace=self.ws, tiled=tiled)
+        # a resident buffer is contiguous and its tile padding is zero (a 0 + b 0 = 0), so the
+        # tiled layout is combined as one row of numel elements
+        flat = (lambda t: t.view(1, -1)) if tiled else (lambda t: t)
+        axpby(flat(self._S), flat(self.Y), a, b, out=flat(self.Y))
+        self.X, self.Y = self.Y, self.X
+        if deviation or mean is not None:
+            self.deviation(mean_out=mean)
+
+    def mix_chebyshev(self, gamma, times=1, eps=None, on_deviation=None):
+        """``Mixer.mix``'s loop with the rounds accelerated by the Chebyshev semi-iteration
+        (``utils.fast_averaging.chebyshev_omegas``): round 1 is the plain ``round()`` -- its bits
+        are the reference's -- and round k >= 2 is ``round_cheb(float32(w_k), float32(1 - w_k))``,
+        w_k iterated in Python floats and 1 - w_k formed in double before rounding.  The stop
+        rule is the reference's, evaluated after each round: stop when ``max_dev < eps and
+        times_done >= times``, from the fused deviation with one 4-byte readback per round
+        (``on_deviation``, optional: called with every evaluated max deviation, np.float32);
+        with ``eps=None`` exactly ``ceil(times)`` rounds run, without readbacks.  Returns the
+        rounds done.
+
+        ``gamma`` is the spectral radius of W - 11^T/n (what ``find_optimal_weights`` and
+        ``spectral_gamma`` return); W must be symmetric.  The per-round contraction becomes
+        gamma / (1 + sqrt(1 - gamma^2)) instead of gamma.  A gamma below the true one can
+        diverge; a gamma above it only converges more slowly.  The deviation sequence is not
+        monotone."""
+        import math
+        from .utils.fast_averaging import chebyshev_omegas
+        gamma = float(gamma)
+        if not 0.0 < gamma < 1.0:
+            raise ValueError(f"mix_chebyshev needs 0 < gamma < 1 (got {gamma})")
+        if not self.W.csr.symmetric:
+            raise ValueError("mix_chebyshev needs a symmetric W (Csr.symmetric)")
+        rounds = math.ceil(times)
+        if eps is None and rounds < 1:
+            return 0
+        omegas = chebyshev_omegas(gamma, max(rounds, 64))
+        done = 0
+        while True:
+            if done == 0:
+                self.round(deviation=eps is not None)
+            else:
+                if done >= len(omegas):
+                    omegas = chebyshev_omegas(gamma, 2 * len(omegas))
+                w = omegas[done]
+                self.round_cheb(np.float32(w), np.float32(1.0 - w), deviation=eps is not None)
+            done += 1
+            if eps is None:
+                if done >= rounds:
+                    return done
+                continue
+            max_dev = np.float32(self.dev_max.item())
+            if on_deviation is not None:
+                on_deviation(max_dev)
+            if max_dev < eps and done >= times:
+                return done
 
     def trace_max_rounds(self):
         """Most rounds one traced pass (``rounds_traced``) can run; 0 = not supported."""

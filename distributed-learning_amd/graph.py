@@ -87,6 +87,24 @@ class Csr:
         cols = np.bincount(self.col, weights=w32, minlength=self.n_src)
         return bool(np.all(np.abs(rows - 1) < 1e-6) and np.all(np.abs(cols - 1) < 1e-6))
 
+    @property
+    def symmetric(self):
+        """W equals its transpose in the fp32 weights the device holds (duplicate entries of a
+        pair summed): what the Chebyshev semi-iteration (``GossipEngine.mix_chebyshev``) needs."""
+        if self.n_src != self.n_rows:
+            return False
+        n = self.n_rows
+        w32 = self.w.astype(np.float32).astype(np.float64)
+        row_id = np.repeat(np.arange(n), np.diff(self.rowptr))
+
+        def entries(r, c):
+            key, inv = np.unique(r * n + c, return_inverse=True)
+            val = np.bincount(inv.reshape(-1), weights=w32, minlength=len(key))
+            return key[val != 0], val[val != 0]
+        k1, v1 = entries(row_id, self.col)
+        k2, v2 = entries(self.col, row_id)
+        return bool(np.array_equal(k1, k2) and np.all(np.abs(v1 - v2) <= 1e-7))
+
     def dense(self):
         W = np.zeros((self.n_rows, self.n_src))
         for a in range(self.n_rows):

@@ -132,6 +132,39 @@ class Mixer(object):
         self.logger.debug('Mixer finished with {} times'.format(times_done))
         return times_done
 
+    def mix_chebyshev(self, gamma, times=1, eps=None):
+        """``mix`` with the rounds accelerated by the Chebyshev semi-iteration
+        (``GossipEngine.mix_chebyshev``): the same flattening, stop rule, log lines, write-back
+        and return value, a fraction of the rounds.  ``gamma`` is the spectral radius of W -
+        11^T/n -- the second value ``utils.fast_averaging.find_optimal_weights`` returns for the
+        weights the topology was built from, or ``spectral_gamma(graph, weights)`` for any
+        others; the topology must be symmetric.  A gamma below the true one can diverge; one
+        above it only converges more slowly.  The deviation tested against ``eps`` is the default
+        metric's (fused into the round); a custom ``dev_metric`` with ``eps`` is refused."""
+        if len(self.topology) <= 1:
+            return 0
+        if eps is not None and self._custom_metric:
+            raise ValueError("mix_chebyshev tests eps against the default deviation metric")
+
+        self.logger.debug('Mixer start with times= {}, eps= {}'.format(times, eps))
+
+        with torch.no_grad():
+            W = self._device_csr()
+            X = self._flatten_all()
+            P = X.shape[1]
+            # the layout mix's round loop would choose
+            T = self._loop_tile_cols(W, P)
+            eng = _engine.GossipEngine(self._csr[0], P, device=self._dev(), X=X,
+                                       layout="tiled" if T else "rows", tile_cols=T, order=None)
+
+            def log(max_dev):
+                self.logger.debug('Mixer calculate max deviation= {}'.format(max_dev))
+            times_done = eng.mix_chebyshev(gamma, times, eps, on_deviation=log)
+            self._write_back(eng.rows())
+
+        self.logger.debug('Mixer finished with {} times'.format(times_done))
+        return times_done
+
     def get_parameters_deviation(self):
         """mixer.py:78-80: dict agent -> ||x_a - mean|| (np.float32, like np.linalg.norm)."""
         with torch.no_grad():

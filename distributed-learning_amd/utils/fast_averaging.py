@@ -81,6 +81,26 @@ def spectral_gamma(graph, weights, vertices=None):
     return float(np.max(np.abs(np.linalg.eigvalsh(Mt))))
 
 
+def chebyshev_omegas(gamma, k):
+    """The first k relaxation factors of the Chebyshev semi-iteration for a symmetric W whose
+    spectral radius off the mean is ``gamma`` (0 < gamma < 1):
+
+        w_1 = 1,  w_2 = 2 / (2 - gamma^2),  w_{j+1} = 4 / (4 - gamma^2 w_j)
+
+    in Python floats.  Round j of the accelerated gossip is x_j = w_j W x_{j-1} + (1 - w_j)
+    x_{j-2}; from w_2 on the factors decrease to 1 + rho^2, rho = gamma / (1 + sqrt(1 -
+    gamma^2)) the per-round contraction the iteration reaches instead of gamma.  The one definition the engine
+    (``GossipEngine.mix_chebyshev``) and the tests use."""
+    gamma = float(gamma)
+    if not 0.0 < gamma < 1.0:
+        raise ValueError(f"gamma must be in (0, 1), got {gamma}")
+    g2 = gamma * gamma
+    out = []
+    for j in range(int(k)):
+        out.append(1.0 if j == 0 else 2.0 / (2.0 - g2) if j == 1 else 4.0 / (4.0 - g2 * out[-1]))
+    return out
+
+
 def _extreme_laplacian_eigs(n, i, j, w, dense_limit=2048):
     """(lambda_2, u_2, lambda_n, u_n) of L(w) (smallest nonzero and largest)."""
     if n <= dense_limit:

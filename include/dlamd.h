@@ -29,6 +29,8 @@
  *                          c3/c5 (torch.optim.SGD, ANNModel autograd)
  *   dl_sgd_round        <- torch.optim.SGD.step of every agent and the Mixer._mix_params_once
  *                          that follows it (Man_Colab.ipynb cells 19-23), in one pass over HBM
+ *   dl_cheb_round, dl_axpby <- (no reference counterpart) Mixer.mix's rounds accelerated by the
+ *                          Chebyshev semi-iteration with gamma of fast_averaging.find_optimal_weights
  *   dl_mlp_eval         <- MasterNode's per-node test statistics (accuracy and loss of every
  *                          node on the shared test_loader, Man_Colab.ipynb cells 21-23) through
  *                          ANNModel.forward (networks/ann_model.py:27-45), all agents at once
@@ -470,6 +472,60 @@ typedef struct dl_sgd_round_args {
 int dl_sgd_round_plan(const dl_sgd_round_args *args, dl_mix_plan *plan);
 int dl_sgd_round(const dl_sgd_round_args *args, void *workspace, size_t ws_bytes,
                  dl_stream_t stream);
+
+/* One round of Chebyshev-accelerated gossip in one HBM pass:  y = a W x + b z, the semi-iteration
+ *   x_1 = W x_0;  x_{k+1} = w_{k+1} W x_k + (1 - w_{k+1}) x_{k-1}
+ *   w_1 = 1, w_2 = 2 / (2 - gamma^2), w_{k+1} = 4 / (4 - gamma^2 w_k)
+ * with x = x_k, z = x_{k-1}, a = w_{k+1}, b = 1 - w_{k+1}.  For a symmetric W whose spectral radius
+ * off the mean is gamma it contracts by gamma / (1 + sqrt(1 - gamma^2)) a round instead of gamma,
+ * and keeps the mean (a + b = 1).  Rounding, per agent row r and column:
+ *   acc = sum_e w_e x[col_e]          left fold from +0.0 in CSR order, product and sum separate
+ *                                     fp32 operations: dl_mix_round's bits with g = NULL
+ *   y   = fl(fl(a acc) + fl(b z[r]))  three separately rounded fp32 operations
+ * i.e. bit for bit dl_mix_round(y = S) followed by dl_axpby(S, z, a, b, out = y), but one launch
+ * that moves 12 B per element (read x, z; write y) instead of two that move 20 B, and no matrix S.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   y may be z itself with ldy == ldz (the intended mode: the thread that reads an element of z
+ *     writes that element of y, so a ping-pong pair holds x_k and x_{k-1} and the round overwrites
+ *     the older one), or x itself with ldy == ldx (a workgroup stages all rows of its columns
+ *     before it writes them), or overlap neither.  x and z are only read.
+ *   z is laid out as x: row-major [n_rows, ldz >= n_params]; column-tiled (mix.tile_cols > 0) ldz
+ *     its block rows (0 = n_rows), 16-byte aligned operands.  Row-major: any n_params >= 1,
+ *     columns [n_params, ld) of y are never written.
+ *   dev_sq / dev_max / mean describe y as dl_mix_round's do, for any W and any z; workspace
+ *     dl_mix_workspace_bytes.
+ *   DL_ERR_INVALID: args NULL; x, y or z NULL ("null x/y/z"); mix.g != NULL ("g must be NULL");
+ *     every argument dl_mix_round itself refuses (W's arrays, strides, tile_cols, alignment of
+ *     tiled operands; the texts say dl_mix_round); ldz out of range ("z laid out as x"); y
+ *     overlapping x or z in any way other than being it ("y overlaps x", "y overlaps z");
+ *     dl_cheb_round_plan with plan NULL.
+ *   DL_ERR_UNSUPPORTED: any halo, partition or lagged-deviation field (halo, n_halo, mean_prev,
+ *     colsum_out, n_local_src, n_halo_blocks, partial_rows_out); rounds that plan path 2, 4 or 5
+ *     (LDS tile kernel only: the caller runs dl_mix_round + dl_axpby).
+ *   DL_ERR_WORKSPACE: as dl_mix_round (deviation outputs without a 16-byte aligned workspace of
+ *     dl_mix_workspace_bytes).
+ *   Stream-ordered, no host synchronisation, no allocation: capturable in a hipGraph.
+ * dl_cheb_round_plan: DL_OK and the configuration the round would run, or the refusal, without
+ * touching the device. */
+typedef struct dl_cheb_round_args {
+    dl_mix_args mix;   /* x, y, W, n_params, ld*, tile_cols, dev_sq, dev_max, mean; g must be NULL;
+                          halo, n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks,
+                          partial_rows_out must be NULL / 0 */
+    const float *z; int64_t ldz;   /* laid out as x (column-tiled: ldz = its block rows, 0 = n_rows) */
+    float a, b;
+} dl_cheb_round_args;
+int dl_cheb_round_plan(const dl_cheb_round_args *args, dl_mix_plan *plan);
+int dl_cheb_round(const dl_cheb_round_args *args, void *workspace, size_t ws_bytes,
+                  dl_stream_t stream);
+/* out[r, j] = fl(fl(a s[r, j]) + fl(b z[r, j])) over n_rows x n_params (row strides lds_, ldz, ldo
+ * >= n_params): dl_cheb_round's second line, so dl_mix_round into s and this call give the fused
+ * round's bits -- the two-launch form, and the fallback where the round does not plan path 1.  out
+ * may be s or z themselves (same stride) or overlap neither; n_rows or n_params 0 is a no-op.
+ * float4 accesses when every pointer is 16-byte aligned and every stride a multiple of 4, with a
+ * scalar tail.  DL_ERR_INVALID: a NULL pointer, negative sizes, n_rows > 65535, a stride below
+ * n_params, out overlapping s or z other than being it. */
+int dl_axpby(const float *s, int64_t lds_, const float *z, int64_t ldz, float a, float b,
+             float *out, int64_t ldo, int32_t n_rows, int64_t n_params, dl_stream_t stream);
 
 /* dst[i] = src[i] for n_floats floats (float4 streaming copy; variant 0: one load in flight
  * per thread, 1: eight, 2: eight + non-temporal stores, 3: four + non-temporal loads and
