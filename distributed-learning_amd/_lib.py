@@ -37,6 +37,9 @@ class DlMixArgs(ctypes.Structure):
 
 
 class DlMixUntilArgs(ctypes.Structure):
+    """dl_mix_until_args.  ``status`` (device int32[2]) receives (rounds done, s): s = 1 the stop
+    rule held, 0 ``max_rounds`` cut the loop (re-enter with the remaining times), 2 the last max
+    deviation is NaN -- it can never pass ``< eps``, so the loop ended there; do not re-enter."""
     _fields_ = [("x", _vp), ("ldx", _i64), ("y", _vp), ("ldy", _i64), ("n_params", _i64),
                 ("W", DlCsr), ("times", _i32), ("use_eps", _i32), ("eps", _f32),
                 ("max_rounds", _i32), ("status", _vp), ("dev_trace", _vp)]

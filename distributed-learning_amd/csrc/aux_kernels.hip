@@ -13,12 +13,14 @@ namespace dl {
 namespace {
 
 // sum over rows in row order (bit-identical to numpy's add.reduce over axis 0), optional /div.
+// The fold starts from +0.0 as numpy's does: a column of -0.0 sums to +0.0 (0 + x is x for every
+// other x, NaN and infinities included).
 __global__ void __launch_bounds__(256) column_sum_kernel(const float *__restrict__ x, int64_t ldx,
                                                          int n_rows, int64_t n_params,
                                                          float *__restrict__ out, float div) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n_params) return;
-    float s = x[p];
+    float s = 0.f + x[p];
     for (int r = 1; r < n_rows; ++r) s = s + x[(int64_t)r * ldx + p];
     out[p] = div > 0.f ? s / div : s;
 }
@@ -46,7 +48,8 @@ __global__ void __launch_bounds__(256) dev_rows_kernel(const float *__restrict__
         partial[(int64_t)blockIdx.x * n_rows + ag] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// numpy std(axis=0): mean = sum/N; var = sum((x-mean)^2)/N; std = sqrt(var); then max over p.
+// numpy std(axis=0): mean = sum/N; var = sum((x-mean)^2)/N; std = sqrt(var); then max over p,
+// which like numpy's keeps a NaN (a column holding a NaN or an inf has a NaN std).
 __global__ void __launch_bounds__(256) max_column_std_kernel(const float *__restrict__ x,
                                                              int64_t ldx, int n_rows,
                                                              int64_t n_params,
@@ -67,11 +70,11 @@ __global__ void __launch_bounds__(256) max_column_std_kernel(const float *__rest
         }
         sd = sqrtf(v / n);
     }
-    for (int m = 32; m >= 1; m >>= 1) sd = fmaxf(sd, __shfl_xor(sd, m));
+    for (int m = 32; m >= 1; m >>= 1) sd = nan_max(sd, __shfl_xor(sd, m));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sd;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float b = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        const float b = nan_max(nan_max(red[0], red[1]), nan_max(red[2], red[3]));
         atomicMax(out_bits, __float_as_uint(b));  // non-negative floats order like their bits
     }
 }

@@ -9,6 +9,12 @@
 
 namespace dl {
 
+// max(a, b) that keeps a NaN, as numpy's max and Python's max over np.linalg.norm values do
+// (fmaxf drops it: a NaN deviation then reads as the 0 the maximum started from).  For two
+// numbers it is fmaxf's value.  A NaN result's sign is not defined; the atomicMax reductions
+// that follow order the bits as unsigned, where a NaN of either sign is above +inf.
+__device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
 // Raise kernel k's dynamic-LDS limit to the whole CU (kLdsBytes), once per (kernel, device):
 // launches then make no attribute call, so they are capturable in a hipGraph and carry no
 // per-launch driver work.

@@ -223,7 +223,7 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
         };
         // mean(W x) = mean(x) when W is doubly stochastic, so mean(y) = mean(a x + b z): reduce
         // the column sums of the inputs under the staging barrier instead of re-mixing the tile
-        const bool mfi = DEV && a.mean_from_inputs;
+        bool mfi = DEV && a.mean_from_inputs;
         float4 cst = zero4();
         // this tile's z, held until its rows are written (FAST)
         float4 cz[FAST ? KV : 1];
@@ -275,6 +275,20 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
             mean_t.y = mean_t.y / n;
             mean_t.z = mean_t.z / n;
             mean_t.w = mean_t.w / n;
+            // a x can overflow where a (W x) does not (|x| above FLT_MAX / |a|: a diverged run),
+            // and then +inf meets -inf here though y and its mean are finite.  A tile with a
+            // mean that is not finite takes the two-pass form, the mean summed from y itself
+            // as numpy does; a tile of finite means keeps this one, bit for bit.
+            // (t - t is 0 for a finite t and NaN for inf or NaN; an inf or NaN component makes t
+            // one, and four finite components whose sum overflows only take the slower form)
+            // Every wave holds all C columns (lane & (C - 1), C divides 64), so the vote of one
+            // wave is the workgroup's: the same in every wave, with no barrier and no LDS.
+            const float t = (mean_t.x + mean_t.y) + (mean_t.z + mean_t.w);
+            if (__any(t - t != 0.f)) {
+                __syncthreads();   // every wave has read scratch before tile_mean rewrites it
+                mfi = false;
+                mean_t = zero4();
+            }
         }
         const __amdgpu_buffer_rsrc_t ry = buf_rsrc(tile_base(a.y, a.yts, tile_id));
         auto store_y = [&](int k, int ag, const float4 &y) {

@@ -772,7 +772,8 @@ __global__ void __launch_bounds__(256) mix_gather_kernel(TileArgs a) {
 // dev_sq[a] = sum_b partial[b][a] (fixed order per lane group, fp64), dev_max = max sqrt.
 // Block = 64 agents x 16 part-lanes; each lane sums parts j, j+16, ... then LDS combine in a
 // fixed order, so the result is deterministic.  dev_max (zeroed by the launcher) takes one
-// atomicMax per block on the bits of a non-negative float.
+// atomicMax per block on the bits of a non-negative float; a NaN deviation stays a NaN through
+// nan_max and, as unsigned bits, is above every number, so dev_max is NaN when any agent's is.
 __global__ void __launch_bounds__(1024) dev_reduce_kernel(const float *__restrict__ partial,
                                                           int nparts, int n_rows,
                                                           float *__restrict__ dev_sq,
@@ -806,7 +807,7 @@ __global__ void __launch_bounds__(1024) dev_reduce_kernel(const float *__restric
     }
     if (j == 0) {
         float mx = sqrtf(f);
-        for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+        for (int m = 32; m >= 1; m >>= 1) mx = nan_max(mx, __shfl_xor(mx, m));
         if (ai == 0 && dev_max) atomicMax(dev_max, __float_as_uint(mx));
     }
 }

@@ -881,7 +881,7 @@ __global__ void __launch_bounds__(kTileThreads) mix_trace_irr_kernel(TileArgs a,
 }
 
 // out[r] = max_a sqrt(sum_b partial[b][r][a]) (fp64 sum in workgroup order, then float, as
-// dev_reduce's dev_sq); one workgroup per round.
+// dev_reduce's dev_sq); one workgroup per round.  NaN when any agent's sum is (nan_max).
 __global__ void __launch_bounds__(1024) trace_reduce_kernel(const float *__restrict__ partial,
                                                             int nparts, int rounds, int n,
                                                             float *__restrict__ out) {
@@ -900,15 +900,15 @@ __global__ void __launch_bounds__(1024) trace_reduce_kernel(const float *__restr
             for (int u = 0; u < 8; ++u) s += (double)v[u];
         }
         for (; b < nparts; ++b) s += (double)partial[((int64_t)b * rounds + r) * n + ag];
-        best = fmaxf(best, sqrtf((float)s));
+        best = nan_max(best, sqrtf((float)s));
     }
 #pragma unroll
-    for (int m = 1; m < 64; m <<= 1) best = fmaxf(best, __shfl_xor(best, m));
+    for (int m = 1; m < 64; m <<= 1) best = nan_max(best, __shfl_xor(best, m));
     if ((tid & 63) == 0) red[tid >> 6] = best;
     __syncthreads();
     if (tid == 0) {
         float m = red[0];
-        for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
+        for (int i = 1; i < 16; ++i) m = nan_max(m, red[i]);
         out[r] = m;
     }
 }

@@ -15,7 +15,8 @@
 // reference, -ffp-contract=off); the column mean is the rows summed in order then divided by N
 // (np.mean axis 0, bit-identical); the norm is a per-lane then tree sum of squares (the
 // reference's np.linalg.norm sums in BLAS order, so this is within rounding of it, not
-// bit-identical); the comparison is float32 against float32(eps), as numpy >= 2 compares an
+// bit-identical; a row whose sum of squares is below 2^-100, where fp32 squares underflow, is
+// summed again in fp64); the comparison is float32 against float32(eps), as numpy >= 2 compares an
 // np.float32 with a Python float (NEP 50).
 #include "dl_internal.h"
 
@@ -32,7 +33,7 @@ __device__ __forceinline__ float mu_wave_sum(float v) {
 
 __device__ __forceinline__ float mu_wave_max(float v) {
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+    for (int m = 32; m >= 1; m >>= 1) v = nan_max(v, __shfl_xor(v, m));
     return v;
 }
 
@@ -95,12 +96,29 @@ __global__ void __launch_bounds__(1024) mix_until_kernel(UntilArgs a) {
                 v += (dx * dx + dy * dy) + (dz * dz + dw * dw);
             }
             v = mu_wave_sum(v);
-            if (lane == 0) devsq[r] = v;
+            float d = sqrtf(v);
+            // Below 2^-100 the fp32 squares are in or near the subnormal range and v has lost
+            // them (at ||x_a - mean|| ~ 1e-38 every one underflows and v is 0): that row's norm
+            // again with the squares and their sum in fp64.  Every larger v -- any but a matrix
+            // of subnormal-sized deviations -- keeps the fp32 value bit for bit.  v is the same
+            // in all lanes of the wave; a NaN v does not compare below.
+            if (v < 0x1p-100f) {
+                double w = 0.0;
+                for (int c = lane; c < C4; c += 64) {
+                    const float4 x = src[r * C4 + c], m = mean[c];
+                    const double dx = x.x - m.x, dy = x.y - m.y, dz = x.z - m.z, dw = x.w - m.w;
+                    w += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+                }
+#pragma unroll
+                for (int m = 32; m >= 1; m >>= 1) w += __shfl_xor(w, m);
+                d = (float)sqrt(w);
+            }
+            if (lane == 0) devsq[r] = d;   // (holds the norm itself)
         }
         __syncthreads();
         if (wave == 0) {
             float m = 0.f;
-            for (int r = lane; r < N; r += 64) m = fmaxf(m, sqrtf(devsq[r]));
+            for (int r = lane; r < N; r += 64) m = nan_max(m, devsq[r]);
             m = mu_wave_max(m);
             if (lane == 0) ctl[0] = m;
         }
@@ -114,14 +132,18 @@ __global__ void __launch_bounds__(1024) mix_until_kernel(UntilArgs a) {
     float4 *dst = img1;
     int done = 0;
     bool stop;
+    // a NaN max deviation can never pass `d < eps`: the loop ends there and says so (status[1]
+    // = 2) instead of running max_rounds rounds of NaN for the caller to re-enter
+    bool nan_dev = false;
     if (a.use_eps) {
         const float d = max_deviation(src);
         if (tid == 0 && a.dev_trace) a.dev_trace[0] = d;
         stop = d < a.eps && done >= a.times;
+        nan_dev = d != d;
     } else {
         stop = done >= a.times;
     }
-    while (!stop && done < a.max_rounds) {
+    while (!stop && !nan_dev && done < a.max_rounds) {
         for (int i = tid; i < E4; i += NT) {
             const int r = i / C4, c = i - r * C4;
             float4 acc = mu_zero4();
@@ -144,6 +166,7 @@ __global__ void __launch_bounds__(1024) mix_until_kernel(UntilArgs a) {
             const float d = max_deviation(src);
             if (tid == 0 && a.dev_trace) a.dev_trace[done] = d;
             stop = d < a.eps && done >= a.times;
+            nan_dev = d != d;
         } else {
             stop = done >= a.times;
         }
@@ -159,7 +182,7 @@ __global__ void __launch_bounds__(1024) mix_until_kernel(UntilArgs a) {
     }
     if (tid == 0) {
         a.status[0] = done;
-        a.status[1] = stop ? 1 : 0;
+        a.status[1] = stop ? 1 : nan_dev ? 2 : 0;
     }
 }
 

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .graph import Csr
+from .stop_rule import below_eps
 
 
 class DeviceCsr:
@@ -458,7 +459,9 @@ def mix_until(W: DeviceCsr, X, Y, times, eps=None, max_rounds=4096, status=None,
               dev_trace=None):
     """``Mixer.mix``'s loop (mixer.py:18-41) in one launch on the current stream: rounds until
     ``(eps is None or max deviation < float32(eps)) and done >= times`` or ``max_rounds``.
-    Y may be X.  ``status`` (device int32[2]) receives (rounds done, 1 if the stop rule held);
+    Y may be X.  ``status`` (device int32[2]) receives (rounds done, s): s = 1 the stop rule held,
+    0 ``max_rounds`` cut the loop, 2 the last max deviation is NaN (the loop ended there: it can
+    never pass ``< eps``, and re-entering would repeat it);
     ``dev_trace`` (device float32[max_rounds + 1], eps only) every evaluated max deviation.
     Does not synchronise."""
     P = X.shape[1]
@@ -924,7 +927,8 @@ class GossipEngine:
         times_done >= times``, from the fused deviation with one 4-byte readback per round
         (``on_deviation``, optional: called with every evaluated max deviation, np.float32);
         with ``eps=None`` exactly ``ceil(times)`` rounds run, without readbacks.  Returns the
-        rounds done.
+        rounds done.  A NaN max deviation can never pass the test: ``FloatingPointError`` naming
+        the round (``stop_rule.below_eps``), X left at that round's iterate.
 
         ``gamma`` is the spectral radius of W - 11^T/n (what ``find_optimal_weights`` and
         ``spectral_gamma`` return); W must be symmetric.  The per-round contraction becomes
@@ -959,7 +963,7 @@ class GossipEngine:
             max_dev = np.float32(self.dev_max.item())
             if on_deviation is not None:
                 on_deviation(max_dev)
-            if max_dev < eps and done >= times:
+            if below_eps(max_dev, eps, done) and done >= times:
                 return done
 
     def trace_max_rounds(self):

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .graph import Csr
+from .stop_rule import below_eps, nan_max_bits_
 
 # the column-tiled pack (dl_step_rows_tiled_peers) and halo mix (dl_mix_args.n_halo_blocks) take
 # at most this many peers' blocks per launch (kMaxPackPeers / kMaxHaloBlocks, dlamd.h)
@@ -374,15 +375,22 @@ class DistTransport:
         return self.dist.batch_isend_irecv(ops) if ops else []
 
     def all_reduce_(self, t, op="sum"):
-        o = self.dist.ReduceOp.SUM if op == "sum" else self.dist.ReduceOp.MAX
-        self.dist.all_reduce(t, op=o, group=self.group)
+        """op "max" is for max deviations: non-negative float32 or NaN, and a NaN on any rank is
+        the result (reduced as integers, stop_rule.nan_max_bits_)."""
+        if op == "sum":
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+        else:
+            self.dist.all_reduce(nan_max_bits_(t), op=self.dist.ReduceOp.MAX, group=self.group)
         return t
 
     def all_reduce_async(self, t, op="sum"):
         """all_reduce_ posted without ordering the current stream after it; ``.wait()`` on the
         returned handle does (RCCL: a stream wait, the host does not block)."""
-        o = self.dist.ReduceOp.SUM if op == "sum" else self.dist.ReduceOp.MAX
-        return self.dist.all_reduce(t, op=o, group=self.group, async_op=True)
+        if op == "sum":
+            return self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group,
+                                        async_op=True)
+        return self.dist.all_reduce(nan_max_bits_(t), op=self.dist.ReduceOp.MAX, group=self.group,
+                                    async_op=True)
 
 
 class _Done:
@@ -932,7 +940,12 @@ class HaloShard:
         re-evaluated on X_k with numpy's row-order column mean over every agent
         (``exact_max_deviation``), so the integer round count does not depend on the lagged
         mean's summation order.  The comparison is float32 against float32(eps), as numpy >= 2
-        compares the reference's np.float32 deviation with a Python float."""
+        compares the reference's np.float32 deviation with a Python float.
+
+        A NaN deviation (the maxima on the device and across ranks keep a NaN) can never pass
+        the test; where the reference would loop for ever, every rank raises
+        ``FloatingPointError`` naming the round k, with X back at X_k -- for k = 0, the state
+        before the call (``stop_rule.below_eps``)."""
         n = int(self.n_total or 0)
         if n <= 1:                       # len(topology) <= 1 (mixer.py:19-20)
             return 0
@@ -956,7 +969,13 @@ class HaloShard:
                         float(ref.abs().max())
                 if gap <= self.TIE_RTOL * abs(float(eps32)) + floor:
                     d = self.exact_max_deviation(self.Y)
-            if d < eps32 and k >= target:
+            try:
+                below = below_eps(d, eps32, k)
+            except FloatingPointError:
+                self.X, self.Y = self.Y, self.X      # back to X_k, the iterate that was measured
+                self._forget_mean()
+                raise
+            if below and k >= target:
                 self.X, self.Y = self.Y, self.X      # back to X_k
                 self._forget_mean()
                 return k

@@ -17,6 +17,11 @@ round is found on the host.  With ``eps=None`` the ``times``
 rounds have nothing in between, so they run as ONE ``dl_mix_rounds`` pass (every round on
 LDS-resident column tiles, bit-identical to ``times`` single rounds).  The results are written
 back into the models once at the end (:34-35, 71-76).
+
+One departure: a max deviation that is NaN (a NaN parameter, or infinities that cancel against
+the column mean) can never pass ``< eps``, and the reference loops for ever on it.  Here every
+route raises ``FloatingPointError`` naming the round (``stop_rule.below_eps``) and the models
+are left as they were before the call.  An infinite deviation is only "not below eps".
 """
 import logging
 import math
@@ -26,6 +31,7 @@ import torch
 
 from ... import engine as _engine
 from ...graph import from_topology, lds_slot_order_native, permuted
+from ...stop_rule import below_eps, nan_max
 
 __all__ = ["Mixer", "basic_deviation_metric"]
 
@@ -200,6 +206,9 @@ class Mixer(object):
                     self.logger.debug('Mixer calculate max deviation= {}'.format(np.float32(d)))
             done += n
             first = False
+            if stopped == 2:   # the device's stop test met a NaN: this raises
+                below_eps(np.float32(trace[n].item()), eps, done)
+                raise FloatingPointError(f"max deviation is NaN after round {done}")
             if stopped:
                 return done
 
@@ -285,7 +294,7 @@ class Mixer(object):
                     if gap <= self._TIE_RTOL * abs(float(eps)) + floor:
                         max_dev = self._recheck_deviation(W, cur, i + 1, P, tiled)
                 self.logger.debug('Mixer calculate max deviation= {}'.format(max_dev))
-                if max_dev < eps and done + i + 1 >= times:
+                if below_eps(max_dev, eps, done + i + 1) and done + i + 1 >= times:
                     stop_at = i + 1
                     break
             if stop_at is None:
@@ -328,11 +337,11 @@ class Mixer(object):
             self.logger.debug('Mixer calculate max deviation= {}'.format(max_dev))
         else:
             max_dev = self._get_max_deviation(X)
-        return max_dev < eps and times_done >= max_times
+        return below_eps(max_dev, eps, times_done) and times_done >= max_times
 
     def _get_max_deviation(self, X):
         devs_list = self._get_deviation_dict(X).values()
-        max_dev = max(devs_list)
+        max_dev = nan_max(devs_list)   # a NaN deviation wherever it stands, as the device's max
         self.logger.debug('Mixer calculate max deviation= {}'.format(max_dev))
         return max_dev
 

@@ -292,7 +292,11 @@ int dl_mix_rounds_trace(const dl_mix_args *args, int32_t rounds, float *trace, v
  * deviation is evaluated before the first round and after each one, as the reference does; the
  * test is float32 against float32(eps) (numpy >= 2 semantics of np.float32 < float).
  * status (device int32[2]) receives {rounds done, 1 if the stop rule held / 0 if max_rounds cut
- * the loop}; a caller continues a cut loop with times' = times - done on y.  dev_trace (nullable,
+ * the loop / 2 if the max deviation of the last evaluation is NaN}; a caller continues a cut loop
+ * with times' = times - done on y.  A NaN max deviation (any NaN parameter, or inf - inf against
+ * the column mean; the maximum keeps a NaN as numpy's does) can never pass `< eps`: the loop
+ * ends at that evaluation, y is the iterate it was taken on, and re-entering would only repeat
+ * it.  An infinite deviation is a number: just not below eps.  dev_trace (nullable,
  * device float[max_rounds + 1], use_eps only) receives the max deviation of every evaluation in
  * order (index 0 = before the first round) for the reference's per-round debug log.  y may be x
  * itself (same ld); otherwise it must not overlap x.  W must be square (col < n_rows). */
@@ -493,7 +497,11 @@ int dl_sgd_round(const dl_sgd_round_args *args, void *workspace, size_t ws_bytes
  *     its block rows (0 = n_rows), 16-byte aligned operands.  Row-major: any n_params >= 1,
  *     columns [n_params, ld) of y are never written.
  *   dev_sq / dev_max / mean describe y as dl_mix_round's do, for any W and any z; workspace
- *     dl_mix_workspace_bytes.
+ *     dl_mix_workspace_bytes.  A doubly stochastic W takes mean(y) as mean(a x + b z) of the
+ *     staged inputs.  Where a x[r] overflows fp32 (|x| above FLT_MAX / |a|: a diverged run) that
+ *     mean can be inf or NaN though y is finite; a tile with such a mean is measured in two
+ *     passes instead, its mean summed from y as for any other W.  Tiles of finite means are
+ *     not affected.
  *   DL_ERR_INVALID: args NULL; x, y or z NULL ("null x/y/z"); mix.g != NULL ("g must be NULL");
  *     every argument dl_mix_round itself refuses (W's arrays, strides, tile_cols, alignment of
  *     tiled operands; the texts say dl_mix_round); ldz out of range ("z laid out as x"); y

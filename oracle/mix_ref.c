@@ -49,9 +49,10 @@ void ref_mix_round(const float *x, int64_t ldx, const float *g, int64_t ldg, flo
     }
 }
 
-/* mean[p] = (sum_r x[r,p]) / n_rows, rows added in order (numpy add.reduce over axis 0). */
+/* mean[p] = (sum_r x[r,p]) / n_rows, rows added in order from +0.0 (numpy add.reduce over axis 0:
+ * a column of -0.0 sums to +0.0). */
 void ref_column_mean(const float *x, int64_t ldx, int32_t n_rows, int64_t n_params, float *mean) {
-    memcpy(mean, x, (size_t)n_params * sizeof(float));
+    for (int64_t p = 0; p < n_params; ++p) mean[p] = 0.0f + x[p];
     for (int32_t r = 1; r < n_rows; ++r)
         for (int64_t p = 0; p < n_params; ++p) mean[p] = mean[p] + x[r * ldx + p];
     const float n = (float)n_rows;

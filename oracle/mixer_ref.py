@@ -48,9 +48,10 @@ def sgd_step(X, G, lr):
 
 
 def column_mean(X):
-    """``np.mean(stack, axis=0)`` (mixer.py:61): rows summed in order, then divided by N."""
+    """``np.mean(stack, axis=0)`` (mixer.py:61): rows summed in order from +0.0 (numpy's
+    add.reduce: a column of -0.0 sums to +0.0), then divided by N."""
     X = np.asarray(X)
-    acc = X[0].copy()
+    acc = X.dtype.type(0) + X[0]
     for r in range(1, X.shape[0]):
         acc = acc + X[r]
     return acc / X.dtype.type(X.shape[0])

@@ -67,7 +67,7 @@ class OracleOps:
 
     def column_sum(self, X):
         Xn = X.numpy()
-        s = Xn[0].copy()
+        s = np.float32(0) + Xn[0]      # numpy's add.reduce starts from +0.0
         for r in range(1, Xn.shape[0]):
             s = s + Xn[r]
         return torch.from_numpy(s)

@@ -135,6 +135,64 @@ def test_halo_mix_stop_rule_two_gloo_ranks(tmp_path, overlap, layout):
     _check_mix(tmp_path, 2, 8, P, _cases(8, P), overlap, layout, want_recheck=(5, 6))
 
 
+def _nan_worker(rank, world, port, side, P, out_dir, w):
+    _init(rank, world, port)
+    from shard_oracle_ops import OracleOps
+    csr = torus_csr(side, side, w)
+    n = side * side
+    parts = sharding.torus_block_partition(side, side, world)
+    plan = sharding.halo_plans(csr, parts)[rank]
+    tr = sharding.dist_transport()
+    # the "max" all-reduce keeps a NaN whichever rank holds it, and orders inf above numbers
+    red = []
+    for vals in ([5.0, float("nan")], [float("nan"), 5.0], [float("inf"), 7.0], [2.0, 3.0],
+                 [-float("nan"), float("inf")]):
+        t = torch.tensor([vals[rank]], dtype=torch.float32)
+        red.append(float(tr.all_reduce_(t, "max")[0]))
+    np.save(os.path.join(out_dir, f"red{rank}.npy"), np.asarray(red))
+    X0 = np.random.default_rng(11).standard_normal((n, P), dtype=np.float32)
+    X0[int(parts[1][3]), 5] = np.nan            # one NaN parameter, in a row rank 1 owns
+    sh = sharding.HaloShard(plan, P, "cpu", tr, n_agents_total=n, ops=OracleOps(),
+                            overlap="chunks", layout="tiled")
+    sh.load_rows(torch.from_numpy(X0[plan.local].copy()))
+    msg = ""
+    try:
+        sh.mix(1, 1e-3, max_rounds=50)
+    except FloatingPointError as err:
+        msg = str(err)
+    with open(os.path.join(out_dir, f"msg{rank}.txt"), "w") as f:
+        f.write(msg)
+    np.save(os.path.join(out_dir, f"x{rank}.npy"), sh.rows().numpy())
+    np.save(os.path.join(out_dir, f"ids{rank}.npy"), plan.local)
+    dist.destroy_process_group()
+
+
+def test_halo_mix_nan_deviation_raises_on_every_rank(tmp_path):
+    """One NaN parameter on rank 1 of 2 gloo ranks: the reference's loop would never end
+    (nan < eps is false); HaloShard.mix raises FloatingPointError naming round 0 on BOTH ranks
+    -- the cross-rank maximum keeps the NaN (the backend's float MAX keeps or drops it by
+    operand order) -- and leaves each rank's rows as they were before the call."""
+    side, P, world = 8, 24, 2
+    torus_csr(side, side)
+    mp.spawn(_nan_worker, args=(world, _free_port(), side, P, str(tmp_path),
+                                _WEIGHT[(side, side)]), nprocs=world, join=True)
+    X0 = np.random.default_rng(11).standard_normal((side * side, P), dtype=np.float32)
+    parts = sharding.torus_block_partition(side, side, world)
+    X0[int(parts[1][3]), 5] = np.nan
+    for r in range(world):
+        red = np.load(tmp_path / f"red{r}.npy")
+        assert np.isnan(red[0]) and np.isnan(red[1]) and np.isnan(red[4]), (r, red)
+        assert red[2] == np.inf and red[3] == 3.0, (r, red)
+        msg = (tmp_path / f"msg{r}.txt").read_text()
+        assert "max deviation is NaN after round 0" in msg, (r, msg)
+        ids = np.load(tmp_path / f"ids{r}.npy")
+        got, want = np.load(tmp_path / f"x{r}.npy"), X0[ids]
+        assert np.isnan(want).sum() == (1 if r == 1 else 0)
+        assert np.array_equal(np.isnan(got), np.isnan(want))
+        ok = ~np.isnan(want)
+        assert np.array_equal(got.view(np.uint32)[ok], want.view(np.uint32)[ok])
+
+
 def _geom_worker(rank, world, port, P, out_dir, w):
     _init(rank, world, port)
     from shard_oracle_ops import OracleOps
