@@ -28,8 +28,7 @@
 // with 64-bit addresses) prefetches nothing and reads z in the pass that writes y.
 #include <type_traits>
 
-#include "dl_internal.h"
-#include "tile_ops.h"
+#include "tile_core.h"
 
 namespace dl {
 namespace {
@@ -60,13 +59,7 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
     const int s = tid / C;
     const int R = a.n_rows;
     const int64_t P = a.n_params;
-    const int nnz = a.nnz;
     const float ca = q.a, cb = q.b;
-
-    float *lw = reinterpret_cast<float *>(smem + a.csr_off);
-    uint16_t *lcol = reinterpret_cast<uint16_t *>(smem + a.csr_off + 4u * (uint32_t)a.n_w);
-    uint16_t *lrp = lcol + nnz;
-    const int reg = a.regular;
 
     // FAST-path byte offsets: lane row s / chunk c; pass k adds k * step
     const uint32_t lc = 16u * (uint32_t)c;
@@ -78,31 +71,19 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
     const uint32_t sy = (uint32_t)SLOTS * a.yrs;
     // staged element of pass k: tile[(s + k * SLOTS) * C + c] = tile[tid + k * NT]
     uint32_t ot = (uint32_t)tid;
-    // byte address of tile t's first element (row 0) in x / z / y
-    auto tile_base = [&](const void *ptr, int64_t ts, int tile_id) {
-        return reinterpret_cast<const char *>(ptr) + (a.tiled ? 0 : a.col_base * 4) +
-               (int64_t)tile_id * ts;
-    };
     float4 *scratch = reinterpret_cast<float4 *>(smem + a.scratch_off);
 
     float4 px[FAST ? KV : 1], pz[PFZ ? KV : 1];
-    // per-agent ||y - mean||^2 accumulators, as mix_tile_kernel keeps them
-    constexpr int ND = KV <= C ? 1 : KV / C;
-    float dacc[ND];
-#pragma unroll
-    for (int k = 0; k < ND; ++k) dacc[k] = 0.f;
-    constexpr bool LD = DEV && C > 1 && KV <= 4;
-    float ldev[LD ? KV : 1];
-#pragma unroll
-    for (int k = 0; k < (LD ? KV : 1); ++k) ldev[k] = 0.f;
+    DevAcc<C, KV, DEV && dev_per_lane(C, KV)> dv;   // per-agent ||y - mean||^2
+    dev_zero(dv);
 
     using PNT = std::integral_constant<int, kBufNT>;
     using PPL = std::integral_constant<int, 0>;
 
     auto prefetch = [&](int tile_id) {
         if (FAST) {
-            const __amdgpu_buffer_rsrc_t rx = buf_rsrc(tile_base(a.x, a.xts, tile_id));
-            const __amdgpu_buffer_rsrc_t rz = buf_rsrc(tile_base(q.z, q.zts, tile_id));
+            const __amdgpu_buffer_rsrc_t rx = buf_rsrc(tile_base(a, a.x, a.xts, tile_id));
+            const __amdgpu_buffer_rsrc_t rz = buf_rsrc(tile_base(a, q.z, q.zts, tile_id));
             // one straight-line loop per load policy (bit 0: x and z non-temporal); x first, so
             // the staging waits on x alone
             auto loads = [&](auto ax) {
@@ -124,91 +105,20 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
         }
     };
 
-    // acc_a = sum_e w_e * x_{col_e} for agent ag, chunk c: left fold in CSR order from +0.0
-    // (mixer.py:47); reads only LDS.  reg5: mix_tile_kernel's form for regular rows of 5 entries
-    // sharing one weight sequence (the same products and sums in the same order).
-    const bool wshared = a.n_w != nnz;
-    const bool reg5 = KV <= 4 && reg == 5 && wshared;
-    float w5[5];
-#pragma unroll
-    for (int e = 0; e < 5; ++e) w5[e] = reg5 ? a.w[e] : 0.f;
-    auto mix_row = [&](int ag) {
-        if (reg5) {
-            uint32_t ci[5];
-#pragma unroll
-            for (int e = 0; e < 5; ++e) ci[e] = lcol[ag * 5 + e];
-            float4 v[5];
-#pragma unroll
-            for (int e = 0; e < 5; ++e) v[e] = tile[ci[e] * C + c];
-            float4 acc = zero4();
-#pragma unroll
-            for (int e = 0; e < 5; ++e) axpy4(acc, w5[e], v[e]);
-            return acc;
-        }
-        int e0, e1;
-        if (reg) {
-            e0 = ag * reg;
-            e1 = e0 + reg;
-        } else {
-            e0 = lrp[ag];
-            e1 = lrp[ag + 1];
-        }
-        const float *wr = wshared ? lw - e0 : lw;
-        float4 acc = zero4();
-        for (int e = e0; e < e1; ++e) axpy4(acc, wr[e], tile[lcol[e] * C + c]);
-        return acc;
-    };
+    // the fold of a row reads only LDS (reg5: at <= 4 rows per thread)
+    const LdsCsr L = lds_csr(smem, a, KV <= 4);
 
-    // column mean of the tile over all agents from per-thread partial sums (mix_tile_kernel's)
-    auto tile_mean = [&](float4 cs) {
-#pragma unroll
-        for (int m = C; m < 64; m <<= 1) cs = shfl_xor4(cs, m);
-        const int wave = tid >> 6, lane = tid & 63;
-        if (lane < C) scratch[wave * C + lane] = cs;
-        __syncthreads();
-        float4 mean = zero4();
-#pragma unroll
-        for (int wv = 0; wv < NT / 64; ++wv) add4(mean, scratch[wv * C + c]);
-        const float n = (float)R;
-        mean.x = mean.x / n;
-        mean.y = mean.y / n;
-        mean.z = mean.z / n;
-        mean.w = mean.w / n;
-        return mean;
-    };
-
-    auto dev_add = [&](int k, float4 y, float4 mean) {  // k may be a runtime pass index
-        const float dx = y.x - mean.x, dy = y.y - mean.y;
-        const float dz = y.z - mean.z, dw = y.w - mean.w;
-        float v = (dx * dx + dy * dy) + (dz * dz + dw * dw);
-        if constexpr (LD) {
-#pragma unroll
-            for (int j = 0; j < KV; ++j) ldev[j] += j == k ? v : 0.f;
-            return;
-        }
-#pragma unroll
-        for (int m = 1; m < C; m <<= 1) v = xor_add(v, m);  // sum over the row group
-        const bool mine = (k % C) == c;
-#pragma unroll
-        for (int j = 0; j < ND; ++j) dacc[j] += (mine && j == k / C) ? v : 0.f;
-    };
-
-    const int trun = a.tile_run;
-    int tile_id = trun ? (int)blockIdx.x * trun : (int)blockIdx.x;
-    const int tile_end = trun ? min(tile_id + trun, a.n_tiles) : a.n_tiles;
-    const int tstep = trun ? 1 : (int)gridDim.x;
-    if (tile_id < tile_end) prefetch(tile_id);
+    TileWalk tw = tile_walk(a);
+    if (tw.id < tw.end) prefetch(tw.id);
     // the LDS CSR is staged behind the first tile's loads; the first staging barrier publishes it
-    for (int i = tid; i < a.n_w; i += NT) lw[i] = a.w[i];
-    for (int i = tid; i < nnz; i += NT) lcol[i] = (uint16_t)a.col[i];
-    if (!a.regular)
-        for (int i = tid; i <= R; i += NT) lrp[i] = (uint16_t)a.rowptr[i];
-    for (; tile_id < tile_end; tile_id += tstep) {
+    stage_csr(L, a, tid);
+    for (; tw.id < tw.end; tw.id += tw.step) {
+        const int tile_id = tw.id;
         // opaque per tile: keeps LICM from hoisting one offset register per pass
         asm volatile("" : "+v"(ox), "+v"(oz), "+v"(oy), "+v"(ot));
         const int64_t col0 = a.col_base + (int64_t)tile_id * T;
-        const int nxt = tile_id + tstep;
-        const __amdgpu_buffer_rsrc_t rzc = buf_rsrc(tile_base(q.z, q.zts, tile_id));
+        const int nxt = tile_id + tw.step;
+        const __amdgpu_buffer_rsrc_t rzc = buf_rsrc(tile_base(a, q.z, q.zts, tile_id));
         auto load_x = [&](int k) {   // (guarded kernel)
             const int r = s + k * SLOTS;
             return ld4(a.x + (int64_t)(r < R ? r : 0) * a.ldx, col0 + 4 * c, P, false);
@@ -258,23 +168,13 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
                 }
             }
         }
-        if (mfi) {
-#pragma unroll
-            for (int m = C; m < 64; m <<= 1) cst = shfl_xor4(cst, m);
-            if ((tid & 63) < C) scratch[(tid >> 6) * C + (tid & 63)] = cst;
-        }
+        if (mfi) col_sums_to_scratch<C>(cst, scratch, tid);
         __syncthreads();
         // the next tile's loads go out first: they land while we mix from LDS
-        if (nxt < tile_end) prefetch(nxt);
+        if (nxt < tw.end) prefetch(nxt);
         float4 mean_t = zero4();
         if (mfi) {
-#pragma unroll
-            for (int wv = 0; wv < NT / 64; ++wv) add4(mean_t, scratch[wv * C + c]);
-            const float n = (float)R;
-            mean_t.x = mean_t.x / n;
-            mean_t.y = mean_t.y / n;
-            mean_t.z = mean_t.z / n;
-            mean_t.w = mean_t.w / n;
+            mean_t = div4(col_sums_from_scratch<C>(scratch, c), (float)R);
             // a x can overflow where a (W x) does not (|x| above FLT_MAX / |a|: a diverged run),
             // and then +inf meets -inf here though y and its mean are finite.  A tile with a
             // mean that is not finite takes the two-pass form, the mean summed from y itself
@@ -290,16 +190,9 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
                 mean_t = zero4();
             }
         }
-        const __amdgpu_buffer_rsrc_t ry = buf_rsrc(tile_base(a.y, a.yts, tile_id));
-        auto store_y = [&](int k, int ag, const float4 &y) {
-            if (FAST) {
-                if (a.nt_store)
-                    buf_st4<kBufNT>(y, ry, oy + (uint32_t)k * sy);
-                else
-                    buf_st4<0>(y, ry, oy + (uint32_t)k * sy);
-            } else {
-                st4(a.y + (int64_t)ag * a.ldy, col0 + 4 * c, P, false, y);
-            }
+        const __amdgpu_buffer_rsrc_t ry = buf_rsrc(tile_base(a, a.y, a.yts, tile_id));
+        auto put_y = [&](int k, int ag, const float4 &y) {
+            store_y<FAST>(a, ry, oy + (uint32_t)k * sy, ag, col0 + 4 * c, y);
         };
         // The two-pass deviation (W not doubly stochastic) needs y twice.  FAST: z is in
         // registers, y is written in the first pass and recomputed in the second.  Guarded: z is
@@ -311,14 +204,14 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
         auto pass = [&](int k, float4 z, bool first) {
             const int ag = s + k * SLOTS;
             if (ag < R) {
-                const float4 y = axpby4(ca, mix_row(ag), cb, z);
+                const float4 y = axpby4(ca, csr_fold<C>(L, tile, ag, c), cb, z);
                 if (first) {
-                    if (FAST || !two) store_y(k, ag, y);
-                    if (mfi) dev_add(k, y, ms);
+                    if (FAST || !two) put_y(k, ag, y);
+                    if (mfi) dev_add(dv, k, y, ms, c);
                     if (two) add4(ms, y);
                 } else {
-                    if (!FAST) store_y(k, ag, y);
-                    dev_add(k, y, ms);
+                    if (!FAST) put_y(k, ag, y);
+                    dev_add(dv, k, y, ms, c);
                 }
             }
         };
@@ -338,7 +231,7 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
         }
         if (mfi && a.mean != nullptr && s == 0) st4(a.mean, col0 + 4 * c, P, FAST, ms);
         if (two) {
-            ms = tile_mean(ms);
+            ms = tile_mean<C>(ms, scratch, tid, c, R);
             if (a.mean != nullptr && s == 0) st4(a.mean, col0 + 4 * c, P, FAST, ms);
             // second LDS pass: recompute y (same order, same bits) instead of holding it
 #pragma unroll 1
@@ -349,25 +242,7 @@ mix_cheb_tile_kernel(TileArgs a, ChebTileArgs q) {
         }
         __syncthreads();  // tile and scratch are rewritten by the next iteration
     }
-    if (LD) {
-#pragma unroll
-        for (int k = 0; k < (LD ? KV : 1); ++k) {
-            float v = ldev[k];
-#pragma unroll
-            for (int m = 1; m < C; m <<= 1) v = xor_add(v, m);   // over the row group
-            const int ag = s + k * SLOTS;
-            if (c == 0 && ag < R) a.dev_partial[(int64_t)blockIdx.x * R + ag] = v;
-        }
-        if (a.dev_max_zero != nullptr && blockIdx.x == 0 && tid == 0) *a.dev_max_zero = 0u;
-    } else if (DEV) {
-#pragma unroll
-        for (int j = 0; j < ND; ++j) {
-            const int k = j * C + c;  // the pass this lane's slot j holds
-            const int ag = s + k * SLOTS;
-            if (k < KV && ag < R) a.dev_partial[(int64_t)blockIdx.x * R + ag] = dacc[j];
-        }
-        if (a.dev_max_zero != nullptr && blockIdx.x == 0 && tid == 0) *a.dev_max_zero = 0u;
-    }
+    if (DEV) dev_epilogue(dv, a, tid, R);
 }
 
 template <int C, int KV, bool FAST>
@@ -375,18 +250,6 @@ hipError_t launch_kv(const TileArgs &a, const ChebTileArgs &q, bool dev, int gri
                      hipStream_t s) {
     return dev ? launch_lds(mix_cheb_tile_kernel<C, KV, true, FAST>, grid, lds, s, a, q)
                : launch_lds(mix_cheb_tile_kernel<C, KV, false, FAST>, grid, lds, s, a, q);
-}
-
-// FAST kernels: every C x KV in {2, 4, 8}; guarded kernels: every C, KV = 8 (plan.h tile_passes)
-template <int C>
-hipError_t launch_c(const TileArgs &a, const ChebTileArgs &q, bool dev, int grid, int lds,
-                    bool fast, hipStream_t s) {
-    if (!fast) return launch_kv<C, kRowsPerThread, false>(a, q, dev, grid, lds, s);
-    switch (tile_passes(C, a.n_src, true)) {
-        case 2: return launch_kv<C, 2, true>(a, q, dev, grid, lds, s);
-        case 4: return launch_kv<C, 4, true>(a, q, dev, grid, lds, s);
-        default: return launch_kv<C, 8, true>(a, q, dev, grid, lds, s);
-    }
 }
 
 }  // namespace
@@ -397,15 +260,15 @@ hipError_t launch_mix_cheb_tile(const TileArgs &a, const ChebTileArgs &q, int ch
     // output row
     if (a.n_src != a.n_rows || a.n_loc != a.n_rows || a.g != nullptr || q.z == nullptr)
         return hipErrorInvalidValue;
-    switch (chunks) {
-        case 1: return launch_c<1>(a, q, dev, grid, lds, fast, s);
-        case 2: return launch_c<2>(a, q, dev, grid, lds, fast, s);
-        case 4: return launch_c<4>(a, q, dev, grid, lds, fast, s);
-        case 8: return launch_c<8>(a, q, dev, grid, lds, fast, s);
-        case 16: return launch_c<16>(a, q, dev, grid, lds, fast, s);
-        case 32: return launch_c<32>(a, q, dev, grid, lds, fast, s);
-        default: return hipErrorInvalidValue;
-    }
+    // FAST kernels: every C x KV in {2, 4, 8}; guarded kernels: every C, KV = 8 (plan.h
+    // tile_passes)
+    return with_chunks(chunks, [&](auto cc) {
+        constexpr int C = decltype(cc)::value;
+        if (!fast) return launch_kv<C, kRowsPerThread, false>(a, q, dev, grid, lds, s);
+        return with_passes(tile_passes(C, a.n_src, true), [&](auto kv) {
+            return launch_kv<C, decltype(kv)::value, true>(a, q, dev, grid, lds, s);
+        });
+    });
 }
 
 }  // namespace dl

@@ -13,26 +13,12 @@
 // (-ffp-contract=off), so K rounds here are bit-identical to K launches of the one-round kernel
 // and to K calls of the reference's fold.  The next tile's X (and G) rows are prefetched into
 // registers while the current tile's rounds run.
-#include "dl_internal.h"
-
 #include <type_traits>
+
+#include "tile_core.h"
 
 namespace dl {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 mm_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-__device__ __forceinline__ float4 mm_nt_load4(const float4 *p) {
-    const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
-    return make_float4(x.x, x.y, x.z, x.w);
-}
-
-__device__ __forceinline__ void mm_nt_store4(float4 v, float4 *p) {
-    f32x4 x = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(x, reinterpret_cast<f32x4 *>(p));
-}
 
 __device__ __forceinline__ const float4 *mm_at(const void *base, uint32_t off) {
     return reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(base) + off);
@@ -60,21 +46,11 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
     const int c = tid & (C - 1);
     const int s = tid / C;
     const int Nr = a.n_rows;
-    const int nnz = a.nnz;
     float4 *img0 = reinterpret_cast<float4 *>(smem);
     float4 *img1 = img0 + (size_t)Nr * C;
-    float *lw = reinterpret_cast<float *>(smem + a.csr_off);
-    uint16_t *lcol = reinterpret_cast<uint16_t *>(smem + a.csr_off + 4u * (uint32_t)a.n_w);
-    uint16_t *lrp = lcol + nnz;
     float4 *scratch = reinterpret_cast<float4 *>(smem + a.scratch_off);
-    const int reg = a.regular;
-    if constexpr (RE == 0) {   // RE > 0 keeps its CSR in registers: nothing staged in LDS
-        for (int i = tid; i < a.n_w; i += NT) lw[i] = a.w[i];
-        for (int i = tid; i < nnz; i += NT) lcol[i] = (uint16_t)a.col[i];
-        if (!reg)
-            for (int i = tid; i <= Nr; i += NT) lrp[i] = (uint16_t)a.rowptr[i];
-    }
-    const bool wshared = a.n_w != nnz;
+    const LdsCsr L = lds_csr(smem, a, false);   // (rows of 5 shared weights take RE = 5)
+    if constexpr (RE == 0) stage_csr(L, a, tid);   // RE > 0 keeps its CSR in registers
 
     uint32_t ox = (uint32_t)s * a.xrs + 16u * c;
     const uint32_t sx = (uint32_t)SLOTS * a.xrs;
@@ -82,44 +58,17 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
     const uint32_t sg = SGD ? (uint32_t)SLOTS * a.grs : 0u;
     uint32_t oy = (uint32_t)s * a.yrs + 16u * c;
     const uint32_t sy = (uint32_t)SLOTS * a.yrs;
-    auto tile_base = [&](const void *p, int64_t ts, int tile_id) {
-        return reinterpret_cast<const char *>(p) + (a.tiled ? 0 : a.col_base * 4) +
-               (int64_t)tile_id * ts;
-    };
 
     float4 px[KV], pg[KV];
     auto prefetch = [&](int tile_id) {
-        const char *xt = tile_base(a.x, a.xts, tile_id);
-        const char *gt = SGD ? tile_base(a.g, a.gts, tile_id) : nullptr;
+        const char *xt = tile_base(a, a.x, a.xts, tile_id);
+        const char *gt = SGD ? tile_base(a, a.g, a.gts, tile_id) : nullptr;
 #pragma unroll
         for (int k = 0; k < KV; ++k) {
             const bool ok = FULL || s + k * SLOTS < Nr;   // ragged: re-read row 0 (L1 hit)
-            px[k] = mm_nt_load4(mm_at(xt, ok ? ox + k * sx : 16u * c));
-            if (SGD) pg[k] = mm_nt_load4(mm_at(gt, ok ? og + k * sg : 16u * c));
+            px[k] = nt_load4(mm_at(xt, ok ? ox + k * sx : 16u * c));
+            if (SGD) pg[k] = nt_load4(mm_at(gt, ok ? og + k * sg : 16u * c));
         }
-    };
-
-    // one agent's output chunk from an LDS image: left fold in CSR order from +0.0 (mixer.py:47)
-    auto mix_row = [&](const float4 *src, int ag) {
-        int e0, e1;
-        if (reg) {
-            e0 = ag * reg;
-            e1 = e0 + reg;
-        } else {
-            e0 = lrp[ag];
-            e1 = lrp[ag + 1];
-        }
-        const float *wr = wshared ? lw - e0 : lw;
-        float4 acc = mm_zero4();
-        for (int e = e0; e < e1; ++e) {
-            const float w = wr[e];
-            const float4 v = src[lcol[e] * C + c];
-            acc.x = acc.x + w * v.x;
-            acc.y = acc.y + w * v.y;
-            acc.z = acc.z + w * v.z;
-            acc.w = acc.w + w * v.w;
-        }
-        return acc;
     };
 
     // register-cached CSR (RE > 0): byte offset of each neighbour's chunk c inside an image
@@ -147,11 +96,11 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
     const bool self0 = RE > 0 && __all(self_ok ? 1 : 0) != 0;
     float4 own[RE > 0 ? KV : 1];
 #pragma unroll
-    for (int k = 0; k < (RE > 0 ? KV : 1); ++k) own[k] = mm_zero4();
+    for (int k = 0; k < (RE > 0 ? KV : 1); ++k) own[k] = zero4();
     auto mix_row_reg = [&](const float4 *src, int k, auto selfc) {
         constexpr bool SELF = decltype(selfc)::value;
         const char *base = reinterpret_cast<const char *>(src);
-        float4 acc = mm_zero4();
+        float4 acc = zero4();
 #pragma unroll
         for (int e = 0; e < (RE > 0 ? RE : 1); ++e) {
             float4 v;
@@ -169,22 +118,20 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
     };
     auto out_row = [&](const float4 *src, int k, int ag, auto selfc) {
         if constexpr (RE > 0) return mix_row_reg(src, k, selfc);
-        return mix_row(src, ag);
+        return csr_fold<C>(L, src, ag, c);
     };
 
-    constexpr int ND = KV <= C ? 1 : KV / C;
-    float dacc[ND];
-#pragma unroll
-    for (int k = 0; k < ND; ++k) dacc[k] = 0.f;
+    DevAcc<C, KV, false> dv;   // per-agent ||y - mean||^2, slot k / C of lane k % C
+    dev_zero(dv);
 
     // The tile loop is rotated: stage (image fill + column mean) of the next tile runs after
     // this tile's output stores, and its prefetch is issued right after, so every path into
     // the fill has the same loads-then-stores order and the fill waits only for the loads
     // (vmcnt(4..7) rather than vmcnt(0), which also drained the previous tile's stores).
     int tile_id = blockIdx.x;
-    float4 mean = mm_zero4();
+    float4 mean = zero4();
     auto stage = [&]() {
-        float4 cst = mm_zero4();
+        float4 cst = zero4();
 #pragma unroll
         for (int k = 0; k < KV; ++k) {
             const int r = s + k * SLOTS;
@@ -217,7 +164,7 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
             if ((tid & 63) < C) scratch[(tid >> 6) * C + (tid & 63)] = cst;
         }
         __syncthreads();
-        mean = mm_zero4();
+        mean = zero4();
         if (DEV) {
 #pragma unroll 2   // (fully unrolled, the 16 reads are hoisted: 64 VGPRs at once, spills)
             for (int wv = 0; wv < NT / 64; ++wv) {
@@ -268,7 +215,7 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
             src = dst;
             dst = const_cast<float4 *>(t);
         }
-        const char *yt = tile_base(a.y, a.yts, tile_id);
+        const char *yt = tile_base(a, a.y, a.yts, tile_id);
 #pragma unroll
         for (int k = 0; k < KV; ++k) {
             const int ag = s + k * SLOTS;
@@ -276,7 +223,7 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
                 const float4 y = out_row(src, k, ag, selfc);
                 float4 *py = const_cast<float4 *>(mm_at(yt, oy + (uint32_t)k * sy));
                 if (MODE == 2 || (MODE == 0 && a.nt_store))
-                    mm_nt_store4(y, py);
+                    nt_store4(y, py);
                 else
                     *py = y;
                 if (DEV) {
@@ -287,7 +234,8 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
                     for (int m = 1; m < C; m <<= 1) v += __shfl_xor(v, m);
                     const bool mine = (k % C) == c;
 #pragma unroll
-                    for (int j = 0; j < ND; ++j) dacc[j] += (mine && j == k / C) ? v : 0.f;
+                    for (int j = 0; j < dev_slots(C, KV); ++j)
+                        dv.dacc[j] += (mine && j == k / C) ? v : 0.f;
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -311,15 +259,7 @@ __global__ void __launch_bounds__(kTileThreads) mix_multi_kernel(TileArgs a, int
     } else {
         tiles(std::false_type{});
     }
-    if (DEV) {
-#pragma unroll
-        for (int j = 0; j < ND; ++j) {
-            const int k = j * C + c;
-            const int ag = s + k * SLOTS;
-            if (k < KV && ag < Nr) a.dev_partial[(int64_t)blockIdx.x * Nr + ag] = dacc[j];
-        }
-        if (a.dev_max_zero != nullptr && blockIdx.x == 0 && tid == 0) *a.dev_max_zero = 0u;
-    }
+    if (DEV) dev_epilogue(dv, a, tid, Nr);
 }
 
 template <int C, int KV, bool SGD, bool DEV, int RE, int MODE>
@@ -358,28 +298,16 @@ hipError_t launch_kv(const TileArgs &a, int rounds, bool sgd, bool dev, int grid
     return launch_re<C, KV, 0>(a, rounds, sgd, dev, grid, lds, s);
 }
 
-template <int C>
-hipError_t launch_c(const TileArgs &a, int rounds, bool sgd, bool dev, int grid, int lds,
-                    hipStream_t s) {
-    const int kv = tile_passes(C, a.n_rows, true);
-    if (kv <= 2) return launch_kv<C, 2>(a, rounds, sgd, dev, grid, lds, s);
-    if (kv <= 4) return launch_kv<C, 4>(a, rounds, sgd, dev, grid, lds, s);
-    return launch_kv<C, 8>(a, rounds, sgd, dev, grid, lds, s);
-}
-
 }  // namespace
 
 hipError_t launch_mix_multi(const TileArgs &a, int chunks, int rounds, bool sgd, bool dev,
                             int grid, int lds, hipStream_t s) {
-    switch (chunks) {
-        case 1: return launch_c<1>(a, rounds, sgd, dev, grid, lds, s);
-        case 2: return launch_c<2>(a, rounds, sgd, dev, grid, lds, s);
-        case 4: return launch_c<4>(a, rounds, sgd, dev, grid, lds, s);
-        case 8: return launch_c<8>(a, rounds, sgd, dev, grid, lds, s);
-        case 16: return launch_c<16>(a, rounds, sgd, dev, grid, lds, s);
-        case 32: return launch_c<32>(a, rounds, sgd, dev, grid, lds, s);
-        default: return hipErrorInvalidValue;
-    }
+    return with_chunks(chunks, [&](auto cc) {
+        constexpr int C = decltype(cc)::value;
+        return with_passes(tile_passes(C, a.n_rows, true), [&](auto kv) {
+            return launch_kv<C, decltype(kv)::value>(a, rounds, sgd, dev, grid, lds, s);
+        });
+    });
 }
 
 }  // namespace dl

@@ -19,8 +19,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "dl_internal.h"
-#include "tile_ops.h"
+#include "tile_core.h"
 
 namespace dl {
 namespace {
@@ -93,11 +92,6 @@ mix_tile_kernel(TileArgs a) {
     const int64_t P = a.n_params;
     const int nnz = a.nnz;
 
-    // staged CSR: n_w weights (all nnz, or one row's when every row shares them), u16 columns,
-    // u16 row_ptr unless the graph is regular
-    float *lw = reinterpret_cast<float *>(smem + a.csr_off);
-    uint16_t *lcol = reinterpret_cast<uint16_t *>(smem + a.csr_off + 4u * (uint32_t)a.n_w);
-    uint16_t *lrp = lcol + nnz;
     // register CSR: weights, and the float4 LDS index (col * C + c < 2^16: the host admits
     // KV <= 4 at C <= 2, i.e. at most 4096 rows) packed two per register
     constexpr int NRC = RD > 0 ? KV * RD : 1;
@@ -188,7 +182,6 @@ mix_tile_kernel(TileArgs a) {
             __syncthreads();
         }
     }
-    const int reg = a.regular;
 
     // FAST-path byte offsets: lane row s / chunk c; pass k adds k * step
     // (row stride = ld*4 in the row-major layout, T*4 in the column-tiled one).  Tile groups
@@ -206,11 +199,6 @@ mix_tile_kernel(TileArgs a) {
     const uint32_t sg = SGD ? (uint32_t)SLOTS * a.grs : 0u;
     uint32_t oy = (uint32_t)s * a.yrs + lc + (uint32_t)gt * (uint32_t)a.yts;
     const uint32_t sy = (uint32_t)SLOTS * a.yrs;
-    // byte address of tile t's first element (row 0) in x / g / y
-    auto tile_base = [&](const void *p, int64_t ts, int tile_id) {
-        return reinterpret_cast<const char *>(p) + (a.tiled ? 0 : a.col_base * 4) +
-               (int64_t)tile_id * grp * ts;
-    };
     float4 *scratch = reinterpret_cast<float4 *>(smem + a.scratch_off);
 
     // HALO == 2 (column-tiled halo, FAST): per pass, the byte offset of this lane's halo row in
@@ -256,21 +244,8 @@ mix_tile_kernel(TileArgs a) {
     float lacc[LAG ? KV : 1];        // LAG: per-pass partial ||x - mean_prev||^2 of the chunk
 #pragma unroll
     for (int k = 0; k < (LAG ? KV : 1); ++k) lacc[k] = 0.f;
-    // per-agent ||y - mean||^2 accumulators, spread over the C lanes of a row group: lane c keeps
-    // the passes k with k % C == c (slot k / C), so ceil(KV / C) registers instead of KV.
-    constexpr int ND = KV <= C ? 1 : KV / C;
-    float dacc[ND];
-#pragma unroll
-    for (int k = 0; k < ND; ++k) dacc[k] = 0.f;
-    // LD (C > 1, KV <= 4): each lane instead keeps its own chunk's partial of every pass's row,
-    // and the row group's C lanes are summed ONCE, after the last tile -- no cross-lane
-    // reduction per pass and tile (log2 C ds_bpermutes per pass: at c3's 256 x 164,608 round
-    // they were 20-30 us of a 117-us launch, scripts/c3_scale_probe.py)
-    constexpr bool LD = DEV && C > 1 && KV <= 4;
-
-    float ldev[LD ? KV : 1];
-#pragma unroll
-    for (int k = 0; k < (LD ? KV : 1); ++k) ldev[k] = 0.f;
+    DevAcc<C, KV, DEV && dev_per_lane(C, KV)> dv;   // per-agent ||y - mean||^2
+    dev_zero(dv);
 
     auto prefetch = [&](int tile_id) {
         const int64_t col0 = a.col_base + (int64_t)tile_id * T;
@@ -283,8 +258,8 @@ mix_tile_kernel(TileArgs a) {
             // local rows from x/g (32-bit offsets), halo rows from the halo buffer (row-major,
             // ldh; or per-peer tiled blocks, hoff/hstr); the per-lane base select keeps every
             // pass straight-line code
-            const char *xt = tile_base(a.x, a.xts, tile_id);
-            const char *gtb = SGD ? tile_base(a.g, a.gts, tile_id) : nullptr;
+            const char *xt = tile_base(a, a.x, a.xts, tile_id, grp);
+            const char *gtb = SGD ? tile_base(a, a.g, a.gts, tile_id, grp) : nullptr;
             const char *ht = reinterpret_cast<const char *>(a.halo) + (HT ? 0 : col0 * 4);
 #pragma unroll
             for (int k = 0; k < KV; ++k) {
@@ -304,9 +279,10 @@ mix_tile_kernel(TileArgs a) {
                 }
             }
         } else if (FAST) {
-            const __amdgpu_buffer_rsrc_t rx = buf_rsrc(tile_base(a.x, a.xts, tile_id));
-            const __amdgpu_buffer_rsrc_t rg = buf_rsrc(SGD ? tile_base(a.g, a.gts, tile_id)
-                                                           : tile_base(a.x, a.xts, tile_id));
+            const __amdgpu_buffer_rsrc_t rx = buf_rsrc(tile_base(a, a.x, a.xts, tile_id, grp));
+            const __amdgpu_buffer_rsrc_t rg =
+                buf_rsrc(SGD ? tile_base(a, a.g, a.gts, tile_id, grp)
+                             : tile_base(a, a.x, a.xts, tile_id, grp));
             // one straight-line loop per load policy (bit 0: x non-temporal, bit 1: g)
             auto loads = [&](auto ax, auto ag) {
 #pragma unroll
@@ -337,43 +313,8 @@ mix_tile_kernel(TileArgs a) {
         }
     };
 
-    // y_a = sum_e w_e * t_{col_e} for agent ag, chunk c: left fold in CSR order from +0.0
-    // (mixer.py:47); reads only LDS.
-    const bool wshared = a.n_w != nnz;  // weight of entry e is lw[e - e0]
-    // regular rows of 5 entries sharing one weight sequence (a degree-4 graph with uniform
-    // weights: c2, c3, c4): the 5 weights in scalar registers from row 0's CSR, the row's 5
-    // column ids and then its 5 tile values read back to back -- 6 LDS round trips a row
-    // become 2 (the same products and sums in the same order: the same bits)
-    const bool reg5 = MIX && RD == 0 && KV <= 4 && reg == 5 && wshared;
-    float w5[5];
-#pragma unroll
-    for (int e = 0; e < 5; ++e) w5[e] = reg5 ? a.w[e] : 0.f;
-    auto mix_row = [&](int ag) {
-        if (reg5) {
-            uint32_t ci[5];
-#pragma unroll
-            for (int e = 0; e < 5; ++e) ci[e] = lcol[ag * 5 + e];
-            float4 v[5];
-#pragma unroll
-            for (int e = 0; e < 5; ++e) v[e] = tile[ci[e] * C + c];
-            float4 acc = zero4();
-#pragma unroll
-            for (int e = 0; e < 5; ++e) axpy4(acc, w5[e], v[e]);
-            return acc;
-        }
-        int e0, e1;
-        if (reg) {
-            e0 = ag * reg;
-            e1 = e0 + reg;
-        } else {
-            e0 = lrp[ag];
-            e1 = lrp[ag + 1];
-        }
-        const float *wr = wshared ? lw - e0 : lw;
-        float4 acc = zero4();
-        for (int e = e0; e < e1; ++e) axpy4(acc, wr[e], tile[lcol[e] * C + c]);
-        return acc;
-    };
+    // the CSR staged in LDS and the fold of a row from it (csr_fold)
+    const LdsCsr L = lds_csr(smem, a, MIX && RD == 0 && KV <= 4);
 
     // the same fold from the register CSR of this thread's pass k: k is a runtime value in the
     // rolled pass loop, so entry e of pass k is picked by a select chain over the KV passes
@@ -518,62 +459,18 @@ mix_tile_kernel(TileArgs a) {
         return xor_add(v, 2);
     };
 
-    // column mean of the tile over all agents from per-thread partial sums: thread -> wave
-    // (lanes with the same c) -> LDS scratch -> every thread sums the 16 wave partials in order
-    // (reading them once per wave and adding across the wave's slot lanes with shuffles instead
-    // measured no faster, profiles/r12)
-    auto tile_mean = [&](float4 cs) {
-#pragma unroll
-        for (int m = C; m < 64; m <<= 1) cs = shfl_xor4(cs, m);
-        const int wave = tid >> 6, lane = tid & 63;
-        if (lane < C) scratch[wave * C + lane] = cs;
-        __syncthreads();
-        float4 mean = zero4();
-#pragma unroll
-        for (int wv = 0; wv < NT / 64; ++wv) add4(mean, scratch[wv * C + c]);
-        const float n = (float)Nr;
-        mean.x = mean.x / n;
-        mean.y = mean.y / n;
-        mean.z = mean.z / n;
-        mean.w = mean.w / n;
-        return mean;
-    };
-
-    auto dev_add = [&](int k, float4 y, float4 mean) {  // k may be a runtime pass index
-        const float dx = y.x - mean.x, dy = y.y - mean.y;
-        const float dz = y.z - mean.z, dw = y.w - mean.w;
-        float v = (dx * dx + dy * dy) + (dz * dz + dw * dw);
-        if constexpr (LD) {   // (k is a runtime pass index: a select per register)
-#pragma unroll
-            for (int j = 0; j < KV; ++j) ldev[j] += j == k ? v : 0.f;
-            return;
-        }
-#pragma unroll
-        for (int m = 1; m < C; m <<= 1) v = xor_add(v, m);  // sum over the row group
-        const bool mine = (k % C) == c;
-#pragma unroll
-        for (int j = 0; j < ND; ++j) dacc[j] += (mine && j == k / C) ? v : 0.f;
-    };
-
-    const int trun = a.tile_run;
-    int tile_id = trun ? (int)blockIdx.x * trun : (int)blockIdx.x;
-    const int tile_end = trun ? min(tile_id + trun, a.n_tiles) : a.n_tiles;
-    const int tstep = trun ? 1 : (int)gridDim.x;
-    if (tile_id < tile_end) prefetch(tile_id);
+    TileWalk tw = tile_walk(a);
+    if (tw.id < tw.end) prefetch(tw.id);
     // the LDS CSR is staged after the first tile's loads are issued: its loads (an L2 hit for
     // every workgroup but the first) then wait behind the tile's instead of delaying them, and
     // the first staging barrier below publishes it
-    if (RD == 0 && MIX) {
-        for (int i = tid; i < a.n_w; i += NT) lw[i] = a.w[i];
-        for (int i = tid; i < nnz; i += NT) lcol[i] = (uint16_t)a.col[i];
-        if (!a.regular)
-            for (int i = tid; i <= Nr; i += NT) lrp[i] = (uint16_t)a.rowptr[i];
-    }
-    for (; tile_id < tile_end; tile_id += tstep) {
+    if (RD == 0 && MIX) stage_csr(L, a, tid);
+    for (; tw.id < tw.end; tw.id += tw.step) {
+        const int tile_id = tw.id;
         // opaque per tile: keeps LICM from hoisting one offset register per pass
         asm volatile("" : "+v"(ox), "+v"(og), "+v"(oy));
         const int64_t col0 = a.col_base + (int64_t)tile_id * T;
-        const int nxt = tile_id + tstep;
+        const int nxt = tile_id + tw.step;
         if (MIX) {
             // stage the (stepped) tile of every source row in LDS
             float4 cst = zero4();  // column partial sums of t (doubly stochastic W only)
@@ -600,11 +497,7 @@ mix_tile_kernel(TileArgs a) {
             // the sum of the whole (doubly stochastic) round's output
             const bool mfi = DEV && a.mean_from_inputs;
             constexpr bool lsum = LAG;
-            if (mfi || lsum) {
-#pragma unroll
-                for (int m = C; m < 64; m <<= 1) cst = shfl_xor4(cst, m);
-                if ((tid & 63) < C) scratch[(tid >> 6) * C + (tid & 63)] = cst;
-            }
+            if (mfi || lsum) col_sums_to_scratch<C>(cst, scratch, tid);
             __syncthreads();
             // the next tile's loads go out first: they land while we mix from LDS.  Issued after
             // the staging barrier: issuing it before (right after the staging writes) measured
@@ -612,20 +505,15 @@ mix_tile_kernel(TileArgs a) {
             // register-head + LDS-tail kernel, one workgroup per CU, 10 % slower too: c4-ba 327
             // vs 361 rounds/s).  And ahead of the tile mean's scratch reads (-1 to -5 us on c3's
             // 100-us round, profiles/r12)
-            if (nxt < tile_end) prefetch(nxt);
+            if (nxt < tw.end) prefetch(nxt);
             float4 mean_t = zero4();
             if (mfi || lsum) {
-#pragma unroll
-                for (int wv = 0; wv < NT / 64; ++wv) add4(mean_t, scratch[wv * C + c]);
+                mean_t = col_sums_from_scratch<C>(scratch, c);
                 if (lsum && s == 0) st4(a.colsum_out, col0 + 4 * c, P, FAST, mean_t);
-                const float n = (float)Nr;
-                mean_t.x = mean_t.x / n;
-                mean_t.y = mean_t.y / n;
-                mean_t.z = mean_t.z / n;
-                mean_t.w = mean_t.w / n;
+                mean_t = div4(mean_t, (float)Nr);
             }
             float *yt = const_cast<float *>(
-                reinterpret_cast<const float *>(tile_base(a.y, a.yts, tile_id)));
+                reinterpret_cast<const float *>(tile_base(a, a.y, a.yts, tile_id, grp)));
             float4 cs = zero4();
             float hy = 0.f;   // hub lane: column hc of row hr (plain store: few rows)
             if (RAG && hub_lane) {
@@ -644,15 +532,8 @@ mix_tile_kernel(TileArgs a) {
                 }
             }
             const __amdgpu_buffer_rsrc_t ry = buf_rsrc(yt);
-            auto store_y = [&](int k, int ag, const float4 &acc) {
-                if (FAST) {
-                    if (a.nt_store)
-                        buf_st4<kBufNT>(acc, ry, oy + (uint32_t)k * sy);
-                    else
-                        buf_st4<0>(acc, ry, oy + (uint32_t)k * sy);
-                } else {
-                    st4(a.y + (int64_t)ag * a.ldy, col0 + 4 * c, P, false, acc);
-                }
+            auto mix_row = [&](int k, int ag) {
+                return RD > 0 ? mix_row_reg(k) : csr_fold<C>(L, tile, ag, c);
             };
             // passes stay rolled: interleaving them would hold KV accumulators at once on top
             // of the 2*KV prefetch registers (and mixing every pass before reducing the tile
@@ -661,11 +542,11 @@ mix_tile_kernel(TileArgs a) {
             for (int k = 0; k < KV; ++k) {
                 const int ag = s + k * SLOTS;
                 if (ag < Nr && !(RAG && ag < NH)) {   // (hub rows: folded by their lanes above)
-                    const float4 acc = RD > 0 ? mix_row_reg(k) : mix_row(ag);
-                    store_y(k, ag, acc);
+                    const float4 acc = mix_row(k, ag);
+                    store_y<FAST>(a, ry, oy + (uint32_t)k * sy, ag, col0 + 4 * c, acc);
                     if (DEV) {
                         if (mfi)
-                            dev_add(k, acc, mean_t);
+                            dev_add(dv, k, acc, mean_t, c);
                         else
                             add4(cs, acc);
                     }
@@ -673,14 +554,14 @@ mix_tile_kernel(TileArgs a) {
             }
             if (mfi && a.mean != nullptr && s == 0) st4(a.mean, col0 + 4 * c, P, FAST, mean_t);
             if (DEV && !mfi) {
-                const float4 mean = tile_mean(cs);
+                const float4 mean = tile_mean<C>(cs, scratch, tid, c, Nr);
                 if (a.mean != nullptr && s == 0) st4(a.mean, col0 + 4 * c, P, FAST, mean);
                 // second LDS pass: recompute y (same order, same bits) instead of holding it
 #pragma unroll 1
                 for (int k = 0; k < KV; ++k) {
                     const int ag = s + k * SLOTS;
                     if (ag < Nr && !(RAG && ag < NH))
-                        dev_add(k, RD > 0 ? mix_row_reg(k) : mix_row(ag), mean);
+                        dev_add(dv, k, mix_row(k, ag), mean, c);
                 }
                 if (RAG && hub_lane) hacc += hub_dev(hy - pick(mean, hc));
             }
@@ -692,48 +573,29 @@ mix_tile_kernel(TileArgs a) {
                 cur[k] = px[k];
                 if (s + k * SLOTS < Nr) add4(cs, cur[k]);
             }
-            if (nxt < tile_end) prefetch(nxt);
-            const float4 mean = tile_mean(cs);
+            if (nxt < tw.end) prefetch(nxt);
+            const float4 mean = tile_mean<C>(cs, scratch, tid, c, Nr);
             if (a.mean != nullptr && s == 0) st4(a.mean, col0 + 4 * c, P, FAST, mean);
 #pragma unroll
             for (int k = 0; k < KV; ++k)
-                if (s + k * SLOTS < Nr) dev_add(k, cur[k], mean);
+                if (s + k * SLOTS < Nr) dev_add(dv, k, cur[k], mean, c);
         }
         __syncthreads();  // tile and scratch are rewritten by the next iteration
     }
     if (LAG) {
 #pragma unroll
         for (int k = 0; k < (LAG ? KV : 1); ++k) {
-            float v = lacc[k];
-#pragma unroll
-            for (int m = 1; m < C; m <<= 1) v = xor_add(v, m);   // over the row group
+            const float v = row_group_sum<C>(lacc[k]);
             const int ag = s + k * SLOTS;   // a local source row
             if (c == 0 && ag < NL) a.dev_partial[(int64_t)blockIdx.x * NL + ag] = v;
         }
         if (a.dev_max_zero != nullptr && blockIdx.x == 0 && tid == 0) *a.dev_max_zero = 0u;
     }
-    if (LD) {
-#pragma unroll
-        for (int k = 0; k < (LD ? KV : 1); ++k) {
-            float v = ldev[k];
-#pragma unroll
-            for (int m = 1; m < C; m <<= 1) v = xor_add(v, m);   // over the row group
-            const int ag = s + k * SLOTS;
-            if (c == 0 && ag < Nr) a.dev_partial[(int64_t)blockIdx.x * Nr + ag] = v;
-        }
-        if (a.dev_max_zero != nullptr && blockIdx.x == 0 && tid == 0) *a.dev_max_zero = 0u;
-    } else if (DEV) {
-#pragma unroll
-        for (int j = 0; j < ND; ++j) {
-            const int k = j * C + c;  // the pass this lane's slot j holds
-            const int ag = s + k * SLOTS;
-            if (k < KV && ag < Nr && !(RAG && ag < NH))
-                a.dev_partial[(int64_t)blockIdx.x * Nr + ag] = dacc[j];
-        }
-        if (RAG && NH > 0) {   // hub rows: every lane of the row holds the same sum (hub_dev)
-            if (hub_lane && hc == 0) a.dev_partial[(int64_t)blockIdx.x * Nr + hr] = hacc;
-        }
-        if (a.dev_max_zero != nullptr && blockIdx.x == 0 && tid == 0) *a.dev_max_zero = 0u;
+    if (DEV) {
+        dev_epilogue(dv, a, tid, Nr, NH);   // (hub rows: their lanes' sums, below)
+        // hub rows: every lane of the row holds the same sum (hub_dev)
+        if (RAG && NH > 0 && hub_lane && hc == 0)
+            a.dev_partial[(int64_t)blockIdx.x * Nr + hr] = hacc;
     }
 }
 
@@ -927,21 +789,6 @@ hipError_t launch_mode(const TileArgs &a, bool sgd, bool dev, bool mix, int grid
                : launch_one<C, KV, false, false, true, 0, FAST>(a, grid, lds, s);
 }
 
-// FAST kernels: every C x KV in {2,4,8}, and tile_kv's KV = 3 (a column-tiled halo mix, C <= 8);
-// guarded kernels: every C, KV = 8.
-template <int C>
-hipError_t launch_fast_c(const TileArgs &a, int kv, bool sgd, bool dev, bool mix, int grid,
-                         int lds, hipStream_t s) {
-    switch (kv) {
-        case 2: return launch_mode<C, 2, true>(a, sgd, dev, mix, grid, lds, s);
-        case 3:
-            if constexpr (C <= 8) return launch_part<C, 3, true, 2>(a, sgd, grid, lds, s);
-            return hipErrorInvalidValue;
-        case 4: return launch_mode<C, 4, true>(a, sgd, dev, mix, grid, lds, s);
-        default: return launch_mode<C, 8, true>(a, sgd, dev, mix, grid, lds, s);
-    }
-}
-
 }  // namespace
 
 // Register-CSR tile kernels, FAST path, no halo rows, C = 1 (T = 4 columns), KV in {2, 4} rows
@@ -986,29 +833,22 @@ hipError_t launch_mix_tile_reg(const TileArgs &a, int chunks, int head, int tail
     }
 }
 
+// FAST kernels: every C x KV in {2,4,8}, and tile_kv's KV = 3 (a column-tiled halo mix, C <= 8);
+// guarded kernels: every C, KV = 8.
 hipError_t launch_mix_tile(const TileArgs &a, int chunks, bool sgd, bool dev, bool mix, int grid,
                            int lds, bool fast, hipStream_t s) {
-    if (fast) {
-        const int kv = tile_kv(chunks, a.n_src, true, mix && a.tiled && a.n_src > a.n_loc);
-        switch (chunks) {
-            case 1: return launch_fast_c<1>(a, kv, sgd, dev, mix, grid, lds, s);
-            case 2: return launch_fast_c<2>(a, kv, sgd, dev, mix, grid, lds, s);
-            case 4: return launch_fast_c<4>(a, kv, sgd, dev, mix, grid, lds, s);
-            case 8: return launch_fast_c<8>(a, kv, sgd, dev, mix, grid, lds, s);
-            case 16: return launch_fast_c<16>(a, kv, sgd, dev, mix, grid, lds, s);
-            case 32: return launch_fast_c<32>(a, kv, sgd, dev, mix, grid, lds, s);
-            default: return hipErrorInvalidValue;
+    return with_chunks(chunks, [&](auto cc) {
+        constexpr int C = decltype(cc)::value;
+        if (!fast) return launch_mode<C, 8, false>(a, sgd, dev, mix, grid, lds, s);
+        const int kv = tile_kv(C, a.n_src, true, mix && a.tiled && a.n_src > a.n_loc);
+        if (kv == 3) {
+            if constexpr (C <= 8) return launch_part<C, 3, true, 2>(a, sgd, grid, lds, s);
+            return hipErrorInvalidValue;
         }
-    }
-    switch (chunks) {
-        case 1: return launch_mode<1, 8, false>(a, sgd, dev, mix, grid, lds, s);
-        case 2: return launch_mode<2, 8, false>(a, sgd, dev, mix, grid, lds, s);
-        case 4: return launch_mode<4, 8, false>(a, sgd, dev, mix, grid, lds, s);
-        case 8: return launch_mode<8, 8, false>(a, sgd, dev, mix, grid, lds, s);
-        case 16: return launch_mode<16, 8, false>(a, sgd, dev, mix, grid, lds, s);
-        case 32: return launch_mode<32, 8, false>(a, sgd, dev, mix, grid, lds, s);
-        default: return hipErrorInvalidValue;
-    }
+        return with_passes(kv, [&](auto kk) {
+            return launch_mode<C, decltype(kk)::value, true>(a, sgd, dev, mix, grid, lds, s);
+        });
+    });
 }
 
 hipError_t allow_full_lds(const void *k) {

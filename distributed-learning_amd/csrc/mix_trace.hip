@@ -16,7 +16,7 @@
 // register-cached), a 16 x C float4 mean scratch.  W must be doubly stochastic: the column mean of every
 // round equals the mean of the pass's input chunk (mean(W t) = mean(t)), as in the fused
 // one-round deviation.
-#include "dl_internal.h"
+#include "tile_core.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -88,18 +88,8 @@ __global__ void __launch_bounds__(kTileThreads) mix_trace_kernel(TileArgs a, int
     float4 *img0 = reinterpret_cast<float4 *>(smem);
     float4 *img1 = img0 + N * C;
     float4 *scratch = reinterpret_cast<float4 *>(smem + a.scratch_off);   // [16][C]
-    float *lw = reinterpret_cast<float *>(smem + a.csr_off);
-    uint16_t *lcol = reinterpret_cast<uint16_t *>(smem + a.csr_off + 4u * (uint32_t)a.n_w);
-    uint16_t *lrp = lcol + a.nnz;
-    const int reg = a.regular;
-    const bool wshared = a.n_w != a.nnz;
-
-    if constexpr (RE == 0) {
-        for (int i = tid; i < a.n_w; i += kTileThreads) lw[i] = a.w[i];
-        for (int i = tid; i < a.nnz; i += kTileThreads) lcol[i] = (uint16_t)a.col[i];
-        if (!reg)
-            for (int i = tid; i <= N; i += kTileThreads) lrp[i] = (uint16_t)a.rowptr[i];
-    }
+    const LdsCsr L = lds_csr(smem, a, false);
+    if constexpr (RE == 0) stage_csr(L, a, tid);
     uint32_t coff[RE > 0 ? RE : 1];
     float wreg[RE > 0 ? RE : 1];
     if constexpr (RE > 0) {
@@ -123,16 +113,16 @@ __global__ void __launch_bounds__(kTileThreads) mix_trace_kernel(TileArgs a, int
             for (int e = 0; e < RE; ++e) fold2(lo, hi, wreg[e], v[e]);
         } else {
             int e0, e1;
-            if (reg) {
-                e0 = tid * reg;
-                e1 = e0 + reg;
+            if (L.reg) {
+                e0 = tid * L.reg;
+                e1 = e0 + L.reg;
             } else {
-                e0 = lrp[tid];
-                e1 = lrp[tid + 1];
+                e0 = L.lrp[tid];
+                e1 = L.lrp[tid + 1];
             }
-            const float *wr = wshared ? lw - e0 : lw;
+            const float *wr = L.wshared ? L.lw - e0 : L.lw;
             const f32x4 *sv = reinterpret_cast<const f32x4 *>(src + c * N);
-            for (int e = e0; e < e1; ++e) fold2(lo, hi, wr[e], sv[lcol[e]]);
+            for (int e = e0; e < e1; ++e) fold2(lo, hi, wr[e], sv[L.lcol[e]]);
         }
     };
     // byte offset of (agent tid, chunk q) in an operand laid out in lc-chunk tiles (lc a power
@@ -427,17 +417,8 @@ __global__ void __launch_bounds__(kTileThreads) mix_trace_wide_kernel(TileArgs a
     float4 *img0 = reinterpret_cast<float4 *>(smem);
     float4 *img1 = img0 + N;
     float4 *scratch = reinterpret_cast<float4 *>(smem + a.scratch_off);   // [16]
-    float *lw = reinterpret_cast<float *>(smem + a.csr_off);
-    uint16_t *lcol = reinterpret_cast<uint16_t *>(smem + a.csr_off + 4u * (uint32_t)a.n_w);
-    uint16_t *lrp = lcol + a.nnz;
-    const int reg = a.regular;
-    const bool wshared = a.n_w != a.nnz;
-    if constexpr (RE == 0) {
-        for (int i = tid; i < a.n_w; i += kTileThreads) lw[i] = a.w[i];
-        for (int i = tid; i < a.nnz; i += kTileThreads) lcol[i] = (uint16_t)a.col[i];
-        if (!reg)
-            for (int i = tid; i <= N; i += kTileThreads) lrp[i] = (uint16_t)a.rowptr[i];
-    }
+    const LdsCsr L = lds_csr(smem, a, false);
+    if constexpr (RE == 0) stage_csr(L, a, tid);
     uint32_t coff[KV][RE > 0 ? RE : 1];
     float wreg[RE > 0 ? RE : 1];
     if constexpr (RE > 0) {
@@ -464,16 +445,16 @@ __global__ void __launch_bounds__(kTileThreads) mix_trace_wide_kernel(TileArgs a
         } else {
             const int ag = s + k * SLOTS;
             int e0, e1;
-            if (reg) {
-                e0 = ag * reg;
-                e1 = e0 + reg;
+            if (L.reg) {
+                e0 = ag * L.reg;
+                e1 = e0 + L.reg;
             } else {
-                e0 = lrp[ag];
-                e1 = lrp[ag + 1];
+                e0 = L.lrp[ag];
+                e1 = L.lrp[ag + 1];
             }
-            const float *wr = wshared ? lw - e0 : lw;
+            const float *wr = L.wshared ? L.lw - e0 : L.lw;
             const f32x4 *sv = reinterpret_cast<const f32x4 *>(src);
-            for (int e = e0; e < e1; ++e) fold2(lo, hi, wr[e], sv[lcol[e]]);
+            for (int e = e0; e < e1; ++e) fold2(lo, hi, wr[e], sv[L.lcol[e]]);
         }
     };
     const int lsh = __builtin_ctz((unsigned)a.lchunks);

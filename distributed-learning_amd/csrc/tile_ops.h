@@ -1,6 +1,8 @@
-// Device helpers of the tile kernels (mix_tile.hip, mix_sgd.hip): 16-byte loads and stores with
-// their cache policies, guarded row accesses, and the fp32 fold and wave-sum primitives.  Every
-// function is force-inlined, in an unnamed namespace: each kernel file gets its own copy.
+// Leaf device helpers of the tile kernels (mix_tile.hip, mix_sgd.hip, mix_cheb.hip, mix_multi.hip
+// and mix_trace.hip, all through tile_core.h, which builds the shared per-tile pieces on them):
+// 16-byte loads and stores with their cache policies, guarded row accesses, and the fp32 fold and
+// wave-sum primitives.  Every function is force-inlined, in an unnamed namespace: each kernel
+// file gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -14,7 +14,7 @@ import torch
 import cheb_oracle as O
 from oracle import cref
 from test_mix_gpu import DEV_RTOL, bits, check_dev, dev_floor, graph_csr
-from test_sgd_round_gpu import SHAPES, dev_t, problem, same
+from test_sgd_round_gpu import FAMILIES, SHAPES, dev_t, family_params, problem, same
 
 pytestmark = pytest.mark.gpu
 
@@ -143,6 +143,27 @@ def test_deviation(cuda, n, P, deg, weights):
         got, (dsq, dmax, mean), _ = run_rounds(cuda, csr, X0, Z0, mode, dev=True)
         same(got[-1], want[-1], f"y ({mode})")
         check_dev(got[-1], dsq, dmax, mean)
+
+
+@pytest.mark.parametrize("n,tiles,weights,dev", FAMILIES)
+def test_kernel_families_without_another_case(cuda, n, tiles, weights, dev):
+    """mix_cheb_tile_kernel's instantiation families that no shape above reaches: those of
+    test_sgd_round_gpu.FAMILIES (the two rounds are shaped alike), full tiles and a 5-column tail
+    at an aligned row stride; the larger tile counts make a workgroup walk to a second tile."""
+    P, deg = family_params(tiles), 4
+    csr, X0, Z0 = operands(n, P, deg, weights)
+    want = oracle(n, P, deg, "y=z", weights)
+    t = [torch.empty(n, P + 3, device=cuda)[:, :P] for _ in range(2)]
+    plan = E().cheb_round_plan(E().DeviceCsr(csr, cuda), t[0], t[1], t[1], deviation=dev)
+    assert plan["tile_cols"] == 128 and plan["n_tiles"] >= tiles, plan
+    assert tiles == 3 or plan["grid"] < tiles, plan   # a workgroup walks more than one tile
+    got, devs, bufs = run_rounds(cuda, csr, X0, Z0, "y=z", ld=P + 3, sentinel=-7.25, dev=dev)
+    for i in range(ROUNDS):
+        same(got[i], want[i], f"y, round {i + 1}")
+    for t in bufs:
+        assert torch.all(t[:, P:] == -7.25)
+    if dev:
+        check_dev(got[-1], *devs)
 
 
 @pytest.mark.parametrize("mode", ["y=z", "apart"])

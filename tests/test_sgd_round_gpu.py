@@ -221,6 +221,52 @@ def test_deviation(cuda, n, P, deg, weights):
     check_dev(got[-1][0], dsq, dmax, mean)
 
 
+# The instantiation families of mix_sgd_tile_kernel that no shape above reaches (tabulated from
+# the launch shaping, profiles/r22/tile_core/README.md), each at the agent count that gives it at
+# the planner's 32 chunks (1024 / 32 = 32 rows a pass) and 128-column tiles:
+#   (n, full tiles, weights, deviation) -> float4 kernel of the full tiles; every launch also runs
+#   the guarded kernel on a 5-column tail, with the same deviation form.
+# Three tiles are three workgroups of one tile each.  The larger counts exceed the grid (256
+# compute units: 129 workgroups for 256 tiles at 8 rows a thread, 257 for 513 at 4), so a
+# workgroup walks to a second tile and prefetches it under the first one's mix.
+FAMILIES = [(64, 3, "regular", False),     # 2 rows a thread, five-weight rows (reg5), no deviation
+            (128, 3, "regular", False),    # 4 rows a thread, reg5, no deviation
+            (128, 3, "random", False),     # 4 rows a thread, CSR rows, no deviation
+            (128, 3, "regular", True),     # 4 rows a thread, reg5, mean from the inputs
+            (256, 3, "random", True),      # 8 rows a thread, two-pass deviation
+            (256, 3, "regular", True),     # 8 rows a thread, mean from the inputs
+            (128, 513, "random", False),   # the walk: 4 rows a thread, no deviation
+            (128, 513, "regular", True),   # the walk: 4 rows a thread, reg5, mean from the inputs
+            (256, 256, "random", False),   # the walk: 8 rows a thread, no deviation
+            (256, 256, "random", True),    # the walk: 8 rows a thread, two-pass deviation
+            (256, 256, "regular", True)]   # the walk: 8 rows a thread, mean from the inputs
+
+
+def family_params(tiles):
+    """Full 128-column tiles and a ragged one of 5; rows 16-byte aligned at ld = P + 3."""
+    return tiles * 128 + 5
+
+
+@pytest.mark.parametrize("n,tiles,weights,dev", FAMILIES)
+def test_kernel_families_without_another_case(cuda, n, tiles, weights, dev):
+    P, deg, opt = family_params(tiles), 4, OPTS[0]
+    csr, X0, Gs = problem(n, P, deg, weights)
+    want = oracle(n, P, deg, opt, weights)
+    t = [torch.empty(n, P + 3, device=cuda)[:, :P] for _ in range(4)]
+    plan = E().sgd_round_plan(E().DeviceCsr(csr, cuda), t[0], t[1], t[2], t[3], deviation=dev,
+                              **opt_kw(opt))
+    assert plan["tile_cols"] == 128 and plan["n_tiles"] >= tiles, plan
+    assert tiles == 3 or plan["grid"] < tiles, plan   # a workgroup walks more than one tile
+    got, devs, bufs = fused_steps(cuda, csr, X0, Gs, opt, ld=P + 3, sentinel=-7.25, dev=dev)
+    for i in range(STEPS):
+        same(got[i][0], want[i][0], f"y, step {i + 1}")
+        same(got[i][1], want[i][1], f"buf, step {i + 1}")
+    for t in bufs:
+        assert torch.all(t[:, P:] == -7.25)
+    if dev:
+        check_dev(got[-1][0], *devs)
+
+
 @pytest.mark.parametrize("n,P,deg", [(33, 129, 4), (64, 4096, 4)])
 def test_first_step_does_not_read_buf(cuda, n, P, deg):
     opt = OPTS[0]
