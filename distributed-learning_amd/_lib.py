@@ -105,6 +105,11 @@ class DlChebRoundArgs(ctypes.Structure):
     _fields_ = [("mix", DlMixArgs), ("z", _vp), ("ldz", _i64), ("a", _f32), ("b", _f32)]
 
 
+class DlTrackRoundArgs(ctypes.Structure):
+    _fields_ = [("mix", DlMixArgs), ("d", _vp), ("ldd", _i64), ("d_out", _vp), ("lddo", _i64),
+                ("g_old", _vp), ("ldq", _i64)]
+
+
 class DlMlpArgs(ctypes.Structure):
     _fields_ = [("n_agents", _i32), ("batch", _i32), ("input_dim", _i32), ("hidden_dim", _i32),
                 ("output_dim", _i32), ("X", _vp), ("ldx", _i64), ("data", _vp), ("s_data", _i64),
@@ -202,6 +207,8 @@ SIGNATURES = {
     "dl_sgd_round": (_i32, [ctypes.POINTER(DlSgdRoundArgs), _vp, _sz, _vp]),
     "dl_cheb_round_plan": (_i32, [ctypes.POINTER(DlChebRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_cheb_round": (_i32, [ctypes.POINTER(DlChebRoundArgs), _vp, _sz, _vp]),
+    "dl_track_round_plan": (_i32, [ctypes.POINTER(DlTrackRoundArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_track_round": (_i32, [ctypes.POINTER(DlTrackRoundArgs), _vp, _sz, _vp]),
     "dl_axpby": (_i32, [_vp, _i64, _vp, _i64, _f32, _f32, _vp, _i64, _i32, _i64, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),

@@ -2,7 +2,7 @@
 // the environment knobs, read once per call.  What an entry point checks and launches is decided
 // by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here their
 // description of a call is turned into launch_* calls and the step after them.  Shaped there:
-// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round), the one-pass
+// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round), the one-pass
 // deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch, dl_lenet_grad
 // and dl_lenet_eval.  The others (dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
 // deviation, the conversions, the step-rows functions, ...) check their own arguments here:
@@ -140,6 +140,9 @@ int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, cons
                 break;
             case dl::kLaunchChebTile:
                 e = dl::launch_mix_cheb_tile(l.t, l.c, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
+                break;
+            case dl::kLaunchTrackTile:
+                e = dl::launch_mix_track_tile(l.t, l.k, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
                 break;
             case dl::kLaunchTileReg:
                 e = dl::launch_mix_tile_reg(l.t, l.chunks, l.head, l.tail_fmt, l.sgd, l.dev, l.grid,
@@ -707,6 +710,25 @@ int dl_cheb_round(const dl_cheb_round_args *args, void *workspace, size_t ws_byt
                                         nullptr, &L, err);
     if (rc) return status(rc, err);
     return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, "mix_cheb_tile_kernel",
+               static_cast<hipStream_t>(stream));
+}
+
+int dl_track_round_plan(const dl_track_round_args *args, dl_mix_plan *plan) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    return status(dl::shape_track_round(args, device_cus(), dl::read_knobs(), nullptr, 0, plan,
+                                        nullptr, err), err);
+}
+
+int dl_track_round(const dl_track_round_args *args, void *workspace, size_t ws_bytes,
+                   dl_stream_t stream) {
+    g_err.clear();
+    dl::Launches L;
+    char err[dl::kErrLen];
+    const int rc = dl::shape_track_round(args, device_cus(), dl::read_knobs(), workspace, ws_bytes,
+                                         nullptr, &L, err);
+    if (rc) return status(rc, err);
+    return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, "mix_track_tile_kernel",
                static_cast<hipStream_t>(stream));
 }
 

@@ -47,6 +47,11 @@ hipError_t launch_mix_sgd_tile(const TileArgs &a, const SgdTileArgs &q, int chun
 // the coefficients (launch.h ChebTileArgs).
 hipError_t launch_mix_cheb_tile(const TileArgs &a, const ChebTileArgs &q, int chunks, bool dev,
                                 int grid, int lds_bytes, bool fast, hipStream_t s);
+// The gradient-tracking round's tile kernel (mix_track.hip) for one launch of a path-1 round
+// shaped by shape_track_round: TileArgs as for launch_mix_tile (g required, no halo rows, no row
+// set), plus the tracker, its output and last step's gradient (launch.h TrackTileArgs).
+hipError_t launch_mix_track_tile(const TileArgs &a, const TrackTileArgs &q, int chunks, bool dev,
+                                 int grid, int lds_bytes, bool fast, hipStream_t s);
 // out = fl(fl(a * s) + fl(b * z)) over n_rows x n_params (aux_kernels.hip); vec: float4 accesses
 hipError_t launch_axpby(const float *src, int64_t lds_, const float *z, int64_t ldz, float a,
                         float b, float *out, int64_t ldo, int n_rows, int64_t n_params, bool vec,

@@ -525,6 +525,98 @@ int shape_cheb_round(const dl_cheb_round_args *a, int n_cus, const Knobs &k, voi
     return DL_OK;
 }
 
+int shape_track_round(const dl_track_round_args *a, int n_cus, const Knobs &k, void *ws,
+                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    // the tracking round's own checks around the round's (y == x allowed, d_out == d below)
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_track_round: args is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y || !a->d || !a->d_out || !m.g || !a->g_old)
+        return fail(err, DL_ERR_INVALID, "dl_track_round: null x/y/d/d_out/g/g_old");
+    if (m.halo || m.n_halo != 0 || m.mean_prev || m.colsum_out || m.n_local_src != 0 ||
+        m.n_halo_blocks != 0 || m.partial_rows_out)
+        return fail(err, DL_ERR_UNSUPPORTED,
+                    "dl_track_round: no halo rows, partition row sets or lagged deviation (halo, "
+                    "n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks, partial_rows_out "
+                    "must be NULL / 0)");
+    int rc = check_mix_args(&m, err, true);
+    if (rc) return rc;
+    const bool tiled = m.tile_cols > 0;
+    const int64_t n = m.W.n_rows;
+    auto bad_ld = [&](int64_t ld) {
+        return tiled ? ld < 0 || (ld > 0 && ld < n) || ld > 65535 * 4 : ld < m.n_params;
+    };
+    if (bad_ld(a->ldd) || bad_ld(a->lddo) || bad_ld(a->ldq))
+        return fail(err, DL_ERR_INVALID, "dl_track_round: d, d_out and g_old laid out as x "
+                                         "(row-major ld >= n_params; column-tiled ld 0 or >= "
+                                         "n_rows)");
+    {
+        const int64_t Tc = m.tile_cols;
+        const int64_t ntl = tiled ? (m.n_params + Tc - 1) / Tc : 0;
+        auto extent = [&](int64_t ld) {
+            return tiled ? (size_t)(((ntl - 1) * (ld ? ld : n) + n) * Tc * 4)
+                         : ((size_t)(n - 1) * ld + m.n_params) * 4;
+        };
+        const size_t dob = extent(a->lddo), yb = extent(m.ldy);
+        const bool in_place = a->d_out == a->d && a->lddo == a->ldd;
+        if (!in_place && overlaps(a->d_out, dob, a->d, extent(a->ldd)))
+            return fail(err, DL_ERR_INVALID, "dl_track_round: d_out overlaps d (d_out may be d "
+                                             "itself with lddo == ldd)");
+        const Span in[] = {{m.x, extent(m.ldx)}, {m.y, yb}, {m.g, extent(m.ldg)},
+                           {a->g_old, extent(a->ldq)}};
+        const char *const in_name[] = {"x", "y", "g", "g_old"};
+        const Span od{a->d_out, dob};
+        const char *const od_name = "d_out";
+        rc = check_disjoint("dl_track_round", &od, &od_name, 1, in, in_name, 4, err);
+        if (rc) return rc;
+        // (y against x and g: check_mix_args)
+        const Span yin[] = {{a->d, extent(a->ldd)}, {a->g_old, extent(a->ldq)}};
+        const char *const yin_name[] = {"d", "g_old"};
+        const Span oy{m.y, yb};
+        const char *const oy_name = "y";
+        rc = check_disjoint("dl_track_round", &oy, &oy_name, 1, yin, yin_name, 2, err);
+        if (rc) return rc;
+    }
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_track_round_plan: plan is NULL");
+    Plan pl;
+    rc = plan_mix(m, n_cus, k, &pl, err);
+    if (rc) return rc;
+    if (pl.pub.path != 1)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_track_round: the fused gradient-tracking round "
+                                             "runs on the LDS tile kernel (plan path 1); this "
+                                             "round plans path %d", pl.pub.path);
+    if (plan) *plan = pl.pub;
+    if (!out) return DL_OK;
+    // do the float4 kernels reach d, d_out and g_old: 16-byte aligned, and row-major rows too,
+    // within the 32-bit offsets of a tile base (as tile_args asks of x, g and y)
+    auto reach = [&](const void *p, int64_t ld) {
+        return aligned16(p) &&
+               (tiled || (ld % 4 == 0 && ((n - 1) * ld + 128) * 4 < ((int64_t)1 << 32)));
+    };
+    rc = shape_round(m, n_cus, k, ws, ws_bytes, out, err,
+                     reach(a->d, a->ldd) && reach(a->d_out, a->lddo) && reach(a->g_old, a->ldq));
+    if (rc) return rc;
+    for (int i = 0; i < out->n; ++i) {
+        Launch &l = out->l[i];
+        if (l.kind != kLaunchTile)
+            return fail(err, DL_ERR_UNSUPPORTED, "dl_track_round: the fused gradient-tracking "
+                                                 "round runs on the LDS tile kernel (plan path 1) "
+                                                 "only");
+        l.kind = kLaunchTrackTile;
+        TrackTileArgs &q = l.k;
+        q.d = a->d;
+        q.ldd = a->ldd;
+        q.d_out = a->d_out;
+        q.lddo = a->lddo;
+        q.q = a->g_old;
+        q.ldq = a->ldq;
+        const int64_t T = 4 * l.chunks;
+        tile_stride(l.t.tiled, a->ldd, l.t.n_rows, T, &q.dts, &q.drs);
+        tile_stride(l.t.tiled, a->lddo, l.t.n_rows, T, &q.dots, &q.dors);
+        tile_stride(l.t.tiled, a->ldq, l.t.n_rows, T, &q.qts, &q.qrs);
+    }
+    return DL_OK;
+}
+
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err) {
     reset(out);

@@ -2,8 +2,8 @@
 // compute units, knobs, workspace pointer and size) that validate a call and describe what it
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
-// rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round and their
-// plan queries),
+// rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round,
+// dl_track_round and their plan queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -130,6 +130,21 @@ struct ChebTileArgs {
     float a, b;
 };
 
+// The gradient-tracking round's operands beside x, g and y (mix_track.hip): the tracker d, its
+// output d_out (d itself or apart) and last step's gradient q, each laid out as x, with their
+// FAST-path strides (tile_stride).  This step's gradient and lr travel in TileArgs (g, lr) as the
+// plain round's do.
+struct TrackTileArgs {
+    const float *d;
+    int64_t ldd;
+    float *d_out;
+    int64_t lddo;
+    const float *q;
+    int64_t ldq;
+    int64_t dts, dots, qts;   // FAST-path tile strides in bytes
+    uint32_t drs, dors, qrs;  // FAST-path row strides in bytes
+};
+
 // One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
 // launch_* functions of dl_internal.h take them.
 enum LaunchKind : int32_t {
@@ -141,6 +156,7 @@ enum LaunchKind : int32_t {
     kLaunchTrace,     // launch_mix_trace(t, chunks, planes, rounds, grid, lds, trace): + its reduce
     kLaunchTraceIrr,  // launch_mix_trace_irr(t, head, gm, narrow, rounds, grid, lds, trace): same
     kLaunchChebTile,  // launch_mix_cheb_tile(t, c, chunks, dev, grid, lds, fast)
+    kLaunchTrackTile, // launch_mix_track_tile(t, k, chunks, dev, grid, lds, fast)
 };
 struct Launch {
     int32_t kind;
@@ -152,6 +168,7 @@ struct Launch {
     TileArgs t;
     SgdTileArgs q;             // kLaunchSgdTile
     ChebTileArgs c;            // kLaunchChebTile
+    TrackTileArgs k;           // kLaunchTrackTile
 };
 // What follows the launches on the stream.
 enum After : int32_t {
@@ -200,6 +217,14 @@ int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void 
 // query, which stops after the plan and needs `plan`.
 int shape_cheb_round(const dl_cheb_round_args *a, int n_cus, const Knobs &k, void *ws,
                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
+// dl_track_round / dl_track_round_plan, in the header's order: the gradient-tracking round's own
+// checks (y == x and d_out == d allowed, every other overlap of an output refused) around the
+// round's, the layouts of d, d_out and g_old, the plan (refused unless path 1; copied to *plan
+// when given), then shape_round with the float4 kernels ruled out when they cannot reach d,
+// d_out or g_old, every launch a kLaunchTrackTile with its TrackTileArgs.  out NULL: the plan
+// query, which stops after the plan and needs `plan`.
+int shape_track_round(const dl_track_round_args *a, int n_cus, const Knobs &k, void *ws,
+                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err);
 int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,

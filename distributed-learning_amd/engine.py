@@ -376,6 +376,61 @@ def cheb_round(W: DeviceCsr, X, Y, Z, a, b, dev_sq=None, dev_max=None, mean=None
     return True
 
 
+def _track_round_args(W, X, Y, D, Dout, G, Gold, lr, dev_sq, dev_max, mean, tiled):
+    if W.n_src != W.n_rows or W.n_local != W.n_rows:
+        raise ValueError("track_round mixes whole rounds only (no halo rows, no partition row set)")
+    if D is None or Dout is None or G is None or Gold is None:
+        raise ValueError("track_round needs the tracker D, its output Dout and the gradients G, "
+                         "Gold")
+    others = (("D", D), ("Dout", Dout), ("Gold", Gold))
+    if tiled is not None:
+        mix = mix_args_tiled(W, tiled[0], tiled[1], X, Y, G, lr, dev_sq, dev_max, mean)
+        lds = [_tiled_ld(t, name, W.n_rows, tiled[0], tiled[1], W.device) for name, t in others]
+    else:
+        mix = mix_args(W, X, Y, G, lr, None, dev_sq, dev_max, mean)
+        for name, t in others:
+            _check(t, name, W.n_rows, X.shape[1], W.device)
+        lds = [_ld(t) for _, t in others]
+    return _lib.DlTrackRoundArgs(mix, _lib.ptr(D), lds[0], _lib.ptr(Dout), lds[1],
+                                 _lib.ptr(Gold), lds[2])
+
+
+def track_round_plan(W: DeviceCsr, X, Y, D, Dout, G, Gold, deviation=False, tiled=None):
+    """dl_track_round_plan: the configuration ``track_round`` would run for these operands, or
+    None when the fused gradient-tracking round does not take them (a plan path other than 1)."""
+    lib = _lib.load()
+    dummy = torch.empty(1, dtype=torch.float32, device=W.device) if deviation else None
+    args = _track_round_args(W, X, Y, D, Dout, G, Gold, 0.0, dummy, dummy, None, tiled)
+    plan = _lib.DlMixPlan()
+    rc = lib.dl_track_round_plan(ctypes.byref(args), ctypes.byref(plan))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "dl_track_round_plan")
+    return {f: getattr(plan, f) for f, _ in plan._fields_}
+
+
+def track_round(W: DeviceCsr, X, Y, D, Dout, G, Gold, lr, dev_sq=None, dev_max=None, mean=None,
+                workspace: Workspace = None, tiled=None):
+    """One gradient-tracking round on the current stream (dl_track_round):
+    Dout = W ((D + G) - Gold), Y = W (X - lr Dout) [+ deviation of Y], both folded as
+    ``mix_round`` folds -- bit for bit ``(D + G) - Gold`` in torch, ``mix_round`` of it into Dout
+    and ``mix_round(X, Y, G=Dout, lr=lr)``, in one pass over HBM.  G is this step's gradient, Gold
+    the last step's (zeros before the first step, with D zero); neither is written.  Dout may be D
+    itself and Y may be X itself.  ``tiled=(n_params, tile_cols)``: every operand in the
+    column-tiled layout.  Returns False, launching nothing, when the fused kernel does not take
+    this round (the caller then runs the three steps)."""
+    lib = _lib.load()
+    P = tiled[0] if tiled is not None else X.shape[1]
+    args = _track_round_args(W, X, Y, D, Dout, G, Gold, lr, dev_sq, dev_max, mean, tiled)
+    workspace = workspace or Workspace(W.device)
+    wp, wn = workspace.ptr_size(lib.dl_mix_workspace_bytes(W.n_rows, 0, P))
+    rc = lib.dl_track_round(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc, "dl_track_round")
+    return True
+
+
 def axpby(S, Z, a, b, out=None):
     """dl_axpby: out = fl(fl(a * S) + fl(b * Z)) over row-major [n, P] tensors (the Chebyshev
     round's second line as a launch of its own).  out may be S or Z; default a new tensor."""
@@ -917,6 +972,41 @@ class GossipEngine:
         self.X, self.Y = self.Y, self.X
         if deviation or mean is not None:
             self.deviation(mean_out=mean)
+
+    def reset_tracker(self):
+        """Zero the gradient tracker ``D`` (the state ``round_track`` starts from; the caller's
+        ``Gold`` of the next round is then zeros too)."""
+        if getattr(self, "D", None) is None:
+            self.D = self._empty()
+        else:
+            self.D.zero_()
+
+    def round_track(self, G, Gold, lr, deviation=False, mean=None):
+        """One gradient-tracking round: D <- W (D + G - Gold), X <- W (X - lr D) with the new D
+        (``track_round``).  ``D`` is the tracker this engine owns, in the resident layout, zero
+        until the first round (``reset_tracker`` zeroes it again) and updated in place; X / Y
+        ping-pong as in ``round``.  G is this step's gradient and Gold the last step's, both in
+        the resident layout (``layout_like``): the caller keeps two buffers, swaps them every step
+        and starts with Gold zero.  Where the fused kernel does not take the round (plan paths 2,
+        4, 5) it runs as ``(D + G) - Gold`` in torch into a scratch matrix, ``mix_round`` of it
+        into D and ``round(G=D, lr)``: the same bits."""
+        if getattr(self, "D", None) is None:
+            self.D = self._empty()
+        tiled = (self.P, self.T) if self.layout == "tiled" else None
+        if track_round(self.W, self.X, self.Y, self.D, self.D, G, Gold, lr,
+                       dev_sq=self.dev_sq if deviation else None,
+                       dev_max=self.dev_max if deviation else None, mean=mean, workspace=self.ws,
+                       tiled=tiled):
+            self.X, self.Y = self.Y, self.X
+            return
+        if getattr(self, "_S", None) is None:
+            self._S = self._empty()
+        # torch's add and sub round once each; the tile padding of a resident buffer is zero and
+        # stays zero ((0 + 0) - 0 and W 0)
+        torch.add(self.D, G, out=self._S)
+        self._S.sub_(Gold)
+        mix_round(self.W, self._S, self.D, workspace=self.ws, tiled=tiled)
+        self.round(G=self.D, lr=lr, deviation=deviation, mean=mean)
 
     def mix_chebyshev(self, gamma, times=1, eps=None, on_deviation=None):
         """``Mixer.mix``'s loop with the rounds accelerated by the Chebyshev semi-iteration

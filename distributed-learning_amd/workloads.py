@@ -510,10 +510,17 @@ class MLPConsensusSGD:
     momentum / weight_decay / dampening / nesterov: the optimizer of Man_Colab.ipynb cell 19
     (``optim.SGD(momentum=0.9, weight_decay=5e-4)``) through ``GossipEngine.round_sgd`` with
     momentum buffers ``M``; needs emit="grad", and ``capture()`` then needs one eager step first
-    (the buffers hold the first gradient).  All zero (the default): the plain step x - lr g."""
+    (the buffers hold the first gradient).  All zero (the default): the plain step x - lr g.
+    tracking=True: gradient tracking instead of the plain step (``GossipEngine.round_track``:
+    D <- W (D + G - G_old), X <- W (X - lr D)), which with a constant lr reaches the optimum of
+    the summed loss where the plain round stalls at a bias set by how much the agents' shards
+    differ.  ``G`` and ``G_alt`` then alternate: ``gradients()`` writes the buffer of the current
+    parity and ``round()`` passes the other one as last step's gradient; the parity flips with the
+    engine's X / Y, so ``capture()`` records one graph per parity as before.  Needs emit="grad"
+    and no momentum / weight_decay."""
 
     def __init__(self, ann, eng, data, labels, lr, deviation=True, emit="auto", sampler=None,
-                 momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False):
+                 momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False, tracking=False):
         if eng.layout == "tiled" and ann.path != "fused":
             raise ValueError("the layered gradients read X row-major: use GossipEngine("
                              "layout='rows') or the fused kernel")
@@ -547,6 +554,9 @@ class MLPConsensusSGD:
         if emit not in ("step", "grad") or (emit == "step" and ann.path != "fused"):
             raise ValueError("emit must be 'grad', or 'step' with the fused gradient kernel")
         self.emit = emit
+        self.tracking = bool(tracking)
+        if self.tracking and (momentum != 0.0 or weight_decay != 0.0 or emit != "grad"):
+            raise ValueError("tracking needs emit='grad' and no momentum / weight_decay")
         self.opt = dict(momentum=float(momentum), dampening=float(dampening),
                         weight_decay=float(weight_decay), nesterov=bool(nesterov))
         self.optimizer = momentum != 0.0 or weight_decay != 0.0
@@ -559,6 +569,11 @@ class MLPConsensusSGD:
         # stays exactly zero -- G is zero there and W 0 = 0 -- and adds exact zeros to the
         # deviation, so results are those of the unpadded round.
         self.G = torch.zeros_like(eng.X)
+        # tracking: the gradient buffer of the other parity (last step's gradient; zero at first)
+        self.G_alt = torch.zeros_like(eng.X) if self.tracking else None
+        self._gpar = 0
+        if self.tracking:
+            eng.reset_tracker()
         self.graphs = None
         self._torch = torch
 
@@ -616,14 +631,24 @@ class MLPConsensusSGD:
         """The gradient phase alone: G (emit="grad") or T = X - lr G (emit="step")."""
         P = self.ann.P
         lr = self.lr if self.emit == "step" else None
+        G = self._g_now()
         if self.eng.layout == "tiled":     # the fused kernel addresses the tiles directly
-            self.ann.gradients(self.eng.X, self.data, self.labels, self.G, lr=lr)
+            self.ann.gradients(self.eng.X, self.data, self.labels, G, lr=lr)
         else:
-            self.ann.gradients(self.eng.X[:, :P], self.data, self.labels, self.G[:, :P], lr=lr)
+            self.ann.gradients(self.eng.X[:, :P], self.data, self.labels, G[:, :P], lr=lr)
+
+    def _g_now(self):
+        """The gradient buffer ``gradients()`` writes: ``G``, or with tracking the one of the
+        current parity."""
+        return self.G_alt if self._gpar else self.G
 
     def round(self):
         """The round phase alone (after ``gradients``)."""
-        if self.optimizer:
+        if self.tracking:
+            g_old = self.G if self._gpar else self.G_alt
+            self.eng.round_track(self._g_now(), g_old, self.lr, deviation=self.deviation)
+            self._gpar ^= 1
+        elif self.optimizer:
             self.eng.round_sgd(self.G, self.M, self.lr, first=self.steps_done == 0,
                                deviation=self.deviation, **self.opt)
         elif self.emit == "step":
@@ -662,6 +687,8 @@ class MLPConsensusSGD:
             self.graphs[self._parity].replay()
             self._parity ^= 1
             self.eng.X, self.eng.Y = self.eng.Y, self.eng.X
+            if self.tracking:
+                self._gpar ^= 1
             self.steps_done += 1
 
     def fit(self, epochs, stat_step=None, test=None):

@@ -31,6 +31,8 @@
  *                          that follows it (Man_Colab.ipynb cells 19-23), in one pass over HBM
  *   dl_cheb_round, dl_axpby <- (no reference counterpart) Mixer.mix's rounds accelerated by the
  *                          Chebyshev semi-iteration with gamma of fast_averaging.find_optimal_weights
+ *   dl_track_round      <- (no reference counterpart) the local step and Mixer.mix's round of
+ *                          the consensus notebooks with gradient tracking: exact at a constant lr
  *   dl_mlp_eval         <- MasterNode's per-node test statistics (accuracy and loss of every
  *                          node on the shared test_loader, Man_Colab.ipynb cells 21-23) through
  *                          ANNModel.forward (networks/ann_model.py:27-45), all agents at once
@@ -525,6 +527,58 @@ typedef struct dl_cheb_round_args {
 int dl_cheb_round_plan(const dl_cheb_round_args *args, dl_mix_plan *plan);
 int dl_cheb_round(const dl_cheb_round_args *args, void *workspace, size_t ws_bytes,
                   dl_stream_t stream);
+/* One gradient-tracking round in one HBM pass (no reference counterpart: the reference's loops run
+ * decentralized gradient descent, X <- W (X - lr G), which with a constant step stalls at a bias
+ * proportional to lr x the heterogeneity of the agents' gradients).  Each agent carries a tracker
+ * d of the network-average gradient and steps along it (adapt-then-combine):
+ *   t  = fl(fl(d + g) - g_old)         element-wise; g this step's gradient, g_old the last one's
+ *   d' = sum_e w_e t[col_e]            dl_mix_round's fold: left fold from +0.0 in CSR order,
+ *                                      product and sum separate fp32 operations
+ *   s  = fl(x - fl(lr d'))             dl_mix_round's fused step with g = d'
+ *   x' = sum_e w_e s[col_e]            the same fold
+ * i.e. bit for bit  T = (D + G) - G_old element-wise, dl_mix_round(x = T, y = D'), dl_mix_round(x =
+ * X, g = D', lr, y = X'),  but one launch that moves 24 B per element (read x, d, g, g_old; write
+ * d', x') instead of at least 36 B and a scratch matrix.  Start from d = 0 and g_old = 0: the
+ * first round then gives d' = W g.  The caller keeps two gradient buffers and swaps them every
+ * step; the round writes neither.  For a doubly stochastic W, mean_a d' = mean_a g at every step
+ * up to rounding, and with a constant lr the iterates reach the optimum of sum_a f_a.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   mix.x / mix.y are x / x', mix.g is g (required), mix.lr is lr.  y may be x itself with ldy ==
+ *     ldx, and d_out may be d itself with lddo == ldd (a workgroup stages all rows of its columns
+ *     before it writes them); otherwise no output overlaps any operand.  g and g_old are only
+ *     read.
+ *   d, d_out and g_old are laid out as x: row-major [n_rows, ld >= n_params]; column-tiled
+ *     (mix.tile_cols > 0) ld their block rows (0 = n_rows), 16-byte aligned operands.  Row-major:
+ *     any n_params >= 1, columns [n_params, ld) of y and d_out are never written.
+ *   dev_sq / dev_max / mean describe x' exactly as dl_mix_round's do; workspace
+ *     dl_mix_workspace_bytes.  A doubly stochastic W takes mean(x') as the mean of the staged s;
+ *     a tile whose mean is then not finite is measured in two passes, as for any other W.
+ *   DL_ERR_INVALID: args NULL; x, y, d, d_out, g or g_old NULL ("null x/y/d/d_out/g/g_old");
+ *     every argument dl_mix_round itself refuses (W's arrays, strides, tile_cols, alignment of
+ *     tiled operands, y overlapping x other than being it, y overlapping g; the texts say
+ *     dl_mix_round); ldd, lddo or ldq out of range ("d, d_out and g_old laid out as x"); d_out
+ *     overlapping d other than being it ("d_out overlaps d"); d_out overlapping x, y, g or g_old
+ *     ("d_out overlaps x" ...); y overlapping d or g_old ("y overlaps d", "y overlaps g_old");
+ *     dl_track_round_plan with plan NULL.
+ *   DL_ERR_UNSUPPORTED: any halo, partition or lagged-deviation field (halo, n_halo, mean_prev,
+ *     colsum_out, n_local_src, n_halo_blocks, partial_rows_out); rounds that plan path 2, 4 or 5
+ *     (LDS tile kernel only: the caller runs the three steps above).
+ *   DL_ERR_WORKSPACE: as dl_mix_round (deviation outputs without a 16-byte aligned workspace of
+ *     dl_mix_workspace_bytes).
+ *   Stream-ordered, no host synchronisation, no allocation: capturable in a hipGraph.
+ * dl_track_round_plan: DL_OK and the configuration the round would run, or the refusal, without
+ * touching the device. */
+typedef struct dl_track_round_args {
+    dl_mix_args mix;   /* x, y, W, g (required), lr, n_params, ld*, tile_cols, dev_sq, dev_max, mean;
+                          halo, n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks,
+                          partial_rows_out must be NULL / 0 */
+    float *d; int64_t ldd;              /* the tracker, laid out as x (read) */
+    float *d_out; int64_t lddo;         /* the new tracker: d itself or apart */
+    const float *g_old; int64_t ldq;    /* last step's gradient, laid out as x */
+} dl_track_round_args;
+int dl_track_round_plan(const dl_track_round_args *args, dl_mix_plan *plan);
+int dl_track_round(const dl_track_round_args *args, void *workspace, size_t ws_bytes,
+                   dl_stream_t stream);
 /* out[r, j] = fl(fl(a s[r, j]) + fl(b z[r, j])) over n_rows x n_params (row strides lds_, ldz, ldo
  * >= n_params): dl_cheb_round's second line, so dl_mix_round into s and this call give the fused
  * round's bits -- the two-launch form, and the fallback where the round does not plan path 1.  out
