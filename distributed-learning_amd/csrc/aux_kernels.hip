@@ -246,7 +246,8 @@ __global__ void __launch_bounds__(256) axpby_kernel(const float *s, int64_t lds_
 
 // ---------------------------------------------------------------- Perron / asyncio round
 // One Jacobi iteration on element i of an [R, TP] tile held in LDS (cur), neighbour sums in
-// socket order (np.sum(list, axis=0): first term, then left fold), then scale.
+// socket order (np.sum(list, axis=0): a left fold from +0.0, so a coordinate where every
+// neighbour holds -0.0 sums to +0.0; 0 + x is x for every other x), then scale.
 template <typename DT>
 __device__ __forceinline__ DT perron_update(const DT *cur, int r, int p, int TP,
                                             const int32_t *__restrict__ rp,
@@ -255,10 +256,7 @@ __device__ __forceinline__ DT perron_update(const DT *cur, int r, int p, int TP,
     const int e0 = rp[r], e1 = rp[r + 1];
     const int cnt = e1 - e0;
     DT s = (DT)0;
-    if (cnt > 0) {
-        s = cur[col[e0] * TP + p];
-        for (int e = e0 + 1; e < e1; ++e) s = s + cur[col[e] * TP + p];
-    }
+    for (int e = e0; e < e1; ++e) s = s + cur[col[e] * TP + p];
     const DT dcoef = (DT)(1.0 - eps * (double)cnt);
     const DT t1 = cur[r * TP + p] * dcoef;
     const DT t2 = (DT)eps * s;

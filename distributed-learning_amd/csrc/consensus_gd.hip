@@ -96,11 +96,8 @@ __global__ void __launch_bounds__(kGdThreads) consensus_gd_kernel(GdArgs a) {
             for (int i = tid; i < E; i += kGdThreads) {
                 const int r = i / F, p = i - r * F;
                 const int e0 = a.rowptr[r], e1 = a.rowptr[r + 1];
-                double s = 0.0;
-                if (e1 > e0) {
-                    s = cur[a.col[e0] * F + p];
-                    for (int e = e0 + 1; e < e1; ++e) s = s + cur[a.col[e] * F + p];
-                }
+                double s = 0.0;   // np.sum folds from +0.0
+                for (int e = e0; e < e1; ++e) s = s + cur[a.col[e] * F + p];
                 const double dcoef = 1.0 - a.eps * (double)(e1 - e0);
                 const double yn = cur[i] * dcoef + a.eps * s;
                 for (int e = e0; e < e1; ++e)

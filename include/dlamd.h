@@ -604,7 +604,10 @@ int dl_stream_copy(const float *src, float *dst, int64_t n_floats, int32_t varia
 
 /* One asyncio consensus round (consensus_asyncio.py:209-312) restated as synchronous Jacobi:
  *   y0_a = v_a * weight_a / mean_weight                              (:231)
- *   y_a <- y_a * (1 - eps*deg_a) + eps * sum_{j in N(a)} y_j           (:295, sum then scale)
+ *   y_a <- y_a * (1 - eps*deg_a) + eps * sum_{j in N(a)} y_j           (:295, sum then scale;
+ *          the sum is np.sum(list, axis=0): a left fold from +0.0 in socket order, so a
+ *          coordinate where every neighbour holds -0.0 sums to +0.0; 0 for an agent without
+ *          neighbours)
  *   flag_a = all_j all_p (y_a - y_j_previous <= conv_eps)              (:297, one-sided)
  * iterated until every flag is set (master DONE, :170-174) or max_iter.  `y` holds the values on
  * entry and the result on exit; iters_out (device int32[1]) receives the iteration count.
