@@ -194,6 +194,31 @@ int deviation_one_pass(const float *x, int64_t ldx, int32_t tile_cols, int32_t n
     return run(L, dev_sq, dev_max, nullptr, "dev tile", s);
 }
 
+// The fused rounds' entry points (launch.h shape_sgd_round, shape_cheb_round, shape_track_round):
+// the plan query, and the round itself.  kernel: `run`'s name for a tile launch.
+template <class Args>
+using ShapeFused = int (*)(const Args *, int, const dl::Knobs &, void *, size_t, dl_mix_plan *,
+                           dl::Launches *, char *);
+template <class Args>
+int fused_round_plan(ShapeFused<Args> shape, const Args *args, dl_mix_plan *plan) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    return status(shape(args, device_cus(), dl::read_knobs(), nullptr, 0, plan, nullptr, err),
+                  err);
+}
+template <class Args>
+int fused_round(ShapeFused<Args> shape, const char *kernel, const Args *args, void *workspace,
+                size_t ws_bytes, dl_stream_t stream) {
+    g_err.clear();
+    dl::Launches L;
+    char err[dl::kErrLen];
+    const int rc = shape(args, device_cus(), dl::read_knobs(), workspace, ws_bytes, nullptr, &L,
+                         err);
+    if (rc) return status(rc, err);
+    return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, kernel,
+               static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 namespace dl {
@@ -676,60 +701,33 @@ int dl_sgd_step(const dl_sgd_args *a, dl_stream_t stream) {
 }
 
 int dl_sgd_round_plan(const dl_sgd_round_args *args, dl_mix_plan *plan) {
-    g_err.clear();
-    char err[dl::kErrLen];
-    return status(dl::shape_sgd_round(args, device_cus(), dl::read_knobs(), nullptr, 0, plan,
-                                      nullptr, err), err);
+    return fused_round_plan(dl::shape_sgd_round, args, plan);
 }
 
 int dl_sgd_round(const dl_sgd_round_args *args, void *workspace, size_t ws_bytes,
                  dl_stream_t stream) {
-    g_err.clear();
-    dl::Launches L;
-    char err[dl::kErrLen];
-    const int rc = dl::shape_sgd_round(args, device_cus(), dl::read_knobs(), workspace, ws_bytes,
-                                       nullptr, &L, err);
-    if (rc) return status(rc, err);
-    return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, "mix_sgd_tile_kernel",
-               static_cast<hipStream_t>(stream));
+    return fused_round(dl::shape_sgd_round, "mix_sgd_tile_kernel", args, workspace, ws_bytes,
+                       stream);
 }
 
 int dl_cheb_round_plan(const dl_cheb_round_args *args, dl_mix_plan *plan) {
-    g_err.clear();
-    char err[dl::kErrLen];
-    return status(dl::shape_cheb_round(args, device_cus(), dl::read_knobs(), nullptr, 0, plan,
-                                       nullptr, err), err);
+    return fused_round_plan(dl::shape_cheb_round, args, plan);
 }
 
 int dl_cheb_round(const dl_cheb_round_args *args, void *workspace, size_t ws_bytes,
                   dl_stream_t stream) {
-    g_err.clear();
-    dl::Launches L;
-    char err[dl::kErrLen];
-    const int rc = dl::shape_cheb_round(args, device_cus(), dl::read_knobs(), workspace, ws_bytes,
-                                        nullptr, &L, err);
-    if (rc) return status(rc, err);
-    return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, "mix_cheb_tile_kernel",
-               static_cast<hipStream_t>(stream));
+    return fused_round(dl::shape_cheb_round, "mix_cheb_tile_kernel", args, workspace, ws_bytes,
+                       stream);
 }
 
 int dl_track_round_plan(const dl_track_round_args *args, dl_mix_plan *plan) {
-    g_err.clear();
-    char err[dl::kErrLen];
-    return status(dl::shape_track_round(args, device_cus(), dl::read_knobs(), nullptr, 0, plan,
-                                        nullptr, err), err);
+    return fused_round_plan(dl::shape_track_round, args, plan);
 }
 
 int dl_track_round(const dl_track_round_args *args, void *workspace, size_t ws_bytes,
                    dl_stream_t stream) {
-    g_err.clear();
-    dl::Launches L;
-    char err[dl::kErrLen];
-    const int rc = dl::shape_track_round(args, device_cus(), dl::read_knobs(), workspace, ws_bytes,
-                                         nullptr, &L, err);
-    if (rc) return status(rc, err);
-    return run(L, args->mix.dev_sq, args->mix.dev_max, nullptr, "mix_track_tile_kernel",
-               static_cast<hipStream_t>(stream));
+    return fused_round(dl::shape_track_round, "mix_track_tile_kernel", args, workspace, ws_bytes,
+                       stream);
 }
 
 int dl_axpby(const float *s, int64_t lds_, const float *z, int64_t ldz, float a, float b,

@@ -98,6 +98,35 @@ void after_reduce(Launches *out, const float *partial, int parts, int rows, bool
     out->max_zeroed = max_zeroed;
 }
 
+// The operand layout of a round whose tile_cols passed check_mix_args: row-major rows of
+// n_params floats, or column tiles of Tc columns.  The rules an operand of n rows "laid out as x"
+// obeys are the fused rounds' (their extra operands all have the round's n_rows rows).
+struct Layout {
+    bool tiled;
+    int64_t n, n_params, Tc, ntl;
+    explicit Layout(const dl_mix_args &a)
+        : tiled(a.tile_cols > 0), n(a.W.n_rows), n_params(a.n_params), Tc(a.tile_cols),
+          ntl(tiled ? (a.n_params + Tc - 1) / Tc : 0) {}
+    // bytes spanned: a tiled operand of `rows` used rows inside blocks of `ld` rows (0 = its own
+    // rows) spans (tiles - 1) block strides plus its used rows of the last tile
+    size_t span(int64_t ld, int64_t rows) const {
+        return tiled ? (size_t)(((ntl - 1) * (ld ? ld : rows) + rows) * Tc * 4)
+                     : ((size_t)(rows - 1) * ld + n_params) * 4;
+    }
+    size_t span(int64_t ld) const { return span(ld, n); }
+    // not laid out as x: row-major ld < n_params; column-tiled block rows neither 0 (its own
+    // rows) nor at least n, or beyond the kernels' block-row bound
+    bool bad_ld(int64_t ld) const {
+        return tiled ? ld < 0 || (ld > 0 && ld < n) || ld > 65535 * 4 : ld < n_params;
+    }
+    // do the float4 kernels reach the operand: 16-byte aligned, and row-major rows too, within
+    // the 32-bit offsets of a tile base (as tile_args asks of x, g and y)
+    bool reach(const void *p, int64_t ld) const {
+        return aligned16(p) &&
+               (tiled || (ld % 4 == 0 && ((n - 1) * ld + 128) * 4 < ((int64_t)1 << 32)));
+    }
+};
+
 }  // namespace
 
 int check_mix_args(const dl_mix_args *a, char *err, bool y_may_be_x) {
@@ -198,22 +227,16 @@ int check_mix_args(const dl_mix_args *a, char *err, bool y_may_be_x) {
                     "dl_mix_round: a lagged halo round without dev_sq leaves its "
                     "deviation as partial rows: pass partial_rows_out (ABI 9) to "
                     "receive their count, or dev_sq for the reduced deviation");
-    // extents: a tiled operand of `rows` used rows inside blocks of `ld` rows spans (tiles - 1)
-    // block strides plus its used rows of the last tile
-    const int64_t Tc = a->tile_cols;
-    const int64_t ntl = tiled ? (a->n_params + Tc - 1) / Tc : 0;
-    auto extent = [&](int64_t ld, int64_t rows) {
-        return tiled ? (size_t)(((ntl - 1) * (ld ? ld : rows) + rows) * Tc * 4)
-                     : ((size_t)(rows - 1) * ld + a->n_params) * 4;
-    };
-    const size_t yb = extent(a->ldy, W.n_rows);
+    const Layout lay(*a);
+    const size_t yb = lay.span(a->ldy, W.n_rows);
     const bool in_place = y_may_be_x && a->y == a->x && a->ldy == a->ldx;
-    if (!in_place && overlaps(a->x, extent(a->ldx, NL), a->y, yb))
+    if (!in_place && overlaps(a->x, lay.span(a->ldx, NL), a->y, yb))
         return fail(err, DL_ERR_INVALID, "dl_mix_round: y overlaps x");
-    if (a->g && overlaps(a->g, extent(a->ldg, NL), a->y, yb))
+    if (a->g && overlaps(a->g, lay.span(a->ldg, NL), a->y, yb))
         return fail(err, DL_ERR_INVALID, "dl_mix_round: y overlaps g");
     if (a->n_halo > 0) {
-        const size_t hb = tiled ? (size_t)(ntl * a->n_halo * Tc * 4) : extent(a->ldh, a->n_halo);
+        const size_t hb = tiled ? (size_t)(lay.ntl * a->n_halo * lay.Tc * 4)
+                                : lay.span(a->ldh, a->n_halo);
         if (overlaps(a->halo, hb, a->y, yb))
             return fail(err, DL_ERR_INVALID, "dl_mix_round: y overlaps halo");
     }
@@ -386,73 +409,103 @@ int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_
     return DL_OK;
 }
 
-int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void *ws,
-                    size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
-    // the momentum round's own checks around the round's (y == x allowed)
-    if (!a) return fail(err, DL_ERR_INVALID, "dl_sgd_round: args is NULL");
-    const dl_mix_args &m = a->mix;
-    if (!m.x || !m.y || !m.g) return fail(err, DL_ERR_INVALID, "dl_sgd_round: null x/y/g");
+namespace {
+
+// A fused round on the LDS tile kernel, as the steps its entry points share see it: the entry
+// point's name and the word for the round in the texts, what its launches are, and the operands
+// it adds to the round's, each laid out as x.
+struct Operand { const void *p; int64_t ld; };
+struct FusedRound {
+    const char *name, *word;
+    LaunchKind kind;
+    const Operand *extra;
+    int n_extra;
+};
+
+// Whole rounds only, then the round's own checks (y == x allowed).
+int whole_round(const FusedRound &r, const dl_mix_args &m, char *err) {
     if (m.halo || m.n_halo != 0 || m.mean_prev || m.colsum_out || m.n_local_src != 0 ||
         m.n_halo_blocks != 0 || m.partial_rows_out)
         return fail(err, DL_ERR_UNSUPPORTED,
-                    "dl_sgd_round: no halo rows, partition row sets or lagged deviation (halo, "
+                    "%s: no halo rows, partition row sets or lagged deviation (halo, "
                     "n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks, partial_rows_out "
-                    "must be NULL / 0)");
-    int rc = check_mix_args(&m, err, true);
+                    "must be NULL / 0)", r.name);
+    return check_mix_args(&m, err, true);
+}
+
+// After the operand checks: the plan, refused unless path 1 and copied to *plan when given; then,
+// unless this is the plan query (out NULL, which needs `plan`), shape_round with the float4
+// kernels ruled out when they cannot reach an extra operand, every launch re-tagged r.kind.  The
+// caller fills the launches' extra args.
+int plan_and_shape(const FusedRound &r, const dl_mix_args &m, int n_cus, const Knobs &k, void *ws,
+                   size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "%s_plan: plan is NULL", r.name);
+    Plan pl;
+    int rc = plan_mix(m, n_cus, k, &pl, err);
     if (rc) return rc;
-    const bool tiled = m.tile_cols > 0;
-    const int64_t n = m.W.n_rows;
-    if (a->momentum != 0.f &&
-        (!a->buf || (tiled ? a->ldb < 0 || (a->ldb > 0 && a->ldb < n) || a->ldb > 65535 * 4
-                           : a->ldb < m.n_params)))
+    if (pl.pub.path != 1)
+        return fail(err, DL_ERR_UNSUPPORTED, "%s: the fused %s round runs on the LDS tile kernel "
+                                             "(plan path 1); this round plans path %d", r.name,
+                    r.word, pl.pub.path);
+    if (plan) *plan = pl.pub;
+    if (!out) return DL_OK;
+    const Layout lay(m);
+    bool vec_ok = true;
+    for (int i = 0; i < r.n_extra; ++i) vec_ok = vec_ok && lay.reach(r.extra[i].p, r.extra[i].ld);
+    rc = shape_round(m, n_cus, k, ws, ws_bytes, out, err, vec_ok);
+    if (rc) return rc;
+    for (int i = 0; i < out->n; ++i) {
+        if (out->l[i].kind != kLaunchTile)
+            return fail(err, DL_ERR_UNSUPPORTED, "%s: the fused %s round runs on the LDS tile "
+                                                 "kernel (plan path 1) only", r.name, r.word);
+        out->l[i].kind = r.kind;
+    }
+    return DL_OK;
+}
+
+// FAST-path strides of an extra operand of launch l
+void extra_stride(const Launch &l, int64_t ld, int64_t *ts, uint32_t *rs) {
+    tile_stride(l.t.tiled, ld, l.t.n_rows, 4 * l.chunks, ts, rs);
+}
+
+}  // namespace
+
+int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void *ws,
+                    size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_sgd_round: args is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y || !m.g) return fail(err, DL_ERR_INVALID, "dl_sgd_round: null x/y/g");
+    // the momentum buffers are an operand only with a momentum
+    const bool mom = a->momentum != 0.f;
+    const Operand buf{a->buf, a->ldb};
+    const FusedRound r{"dl_sgd_round", "momentum", kLaunchSgdTile, &buf, mom ? 1 : 0};
+    int rc = whole_round(r, m, err);
+    if (rc) return rc;
+    const Layout lay(m);
+    if (mom && (!a->buf || lay.bad_ld(a->ldb)))
         return fail(err, DL_ERR_INVALID, "dl_sgd_round: momentum needs a buffer laid out as x "
                                          "(row-major ldb >= n_params; column-tiled ldb 0 or >= "
                                          "n_rows)");
     if (a->nesterov && (a->momentum <= 0.f || a->dampening != 0.f))
         return fail(err, DL_ERR_INVALID, "dl_sgd_round: Nesterov momentum requires a momentum and "
                                          "zero dampening");
-    if (a->momentum != 0.f) {
-        const int64_t Tc = m.tile_cols;
-        const int64_t ntl = tiled ? (m.n_params + Tc - 1) / Tc : 0;
-        auto extent = [&](int64_t ld) {
-            return tiled ? (size_t)(((ntl - 1) * (ld ? ld : n) + n) * Tc * 4)
-                         : ((size_t)(n - 1) * ld + m.n_params) * 4;
-        };
-        const size_t bb = extent(a->ldb);
-        if (overlaps(a->buf, bb, m.x, extent(m.ldx)) || overlaps(a->buf, bb, m.y, extent(m.ldy)) ||
-            overlaps(a->buf, bb, m.g, extent(m.ldg)))
+    if (mom) {
+        const size_t bb = lay.span(a->ldb);
+        if (overlaps(a->buf, bb, m.x, lay.span(m.ldx)) ||
+            overlaps(a->buf, bb, m.y, lay.span(m.ldy)) ||
+            overlaps(a->buf, bb, m.g, lay.span(m.ldg)))
             return fail(err, DL_ERR_INVALID, "dl_sgd_round: buf overlaps x, y or g");
     }
-    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_sgd_round_plan: plan is NULL");
-    Plan pl;
-    rc = plan_mix(m, n_cus, k, &pl, err);
-    if (rc) return rc;
-    if (pl.pub.path != 1)
-        return fail(err, DL_ERR_UNSUPPORTED, "dl_sgd_round: the fused momentum round runs on the "
-                                             "LDS tile kernel (plan path 1); this round plans "
-                                             "path %d", pl.pub.path);
-    if (plan) *plan = pl.pub;
-    if (!out) return DL_OK;
-    // do the float4 kernels reach the momentum buffers: 16-byte aligned, and row-major rows too,
-    // within the 32-bit offsets of a tile base (as tile_args asks of x, g and y)
-    const bool buf_vec =
-        a->momentum == 0.f ||
-        (aligned16(a->buf) && (tiled || (a->ldb % 4 == 0 &&
-                                         ((n - 1) * a->ldb + 128) * 4 < ((int64_t)1 << 32))));
-    rc = shape_round(m, n_cus, k, ws, ws_bytes, out, err, buf_vec);
-    if (rc) return rc;
+    rc = plan_and_shape(r, m, n_cus, k, ws, ws_bytes, plan, out, err);
+    if (rc || !out) return rc;
     for (int i = 0; i < out->n; ++i) {
         Launch &l = out->l[i];
-        if (l.kind != kLaunchTile)
-            return fail(err, DL_ERR_UNSUPPORTED, "dl_sgd_round: the fused momentum round runs on "
-                                                 "the LDS tile kernel (plan path 1) only");
-        l.kind = kLaunchSgdTile;
         l.q.p = SgdParams{m.lr, a->momentum, a->dampening, a->weight_decay,
                           a->first ? 1 : 0, a->nesterov ? 1 : 0};
-        if (a->momentum != 0.f) {
+        if (mom) {
             l.q.buf = a->buf;
             l.q.ldb = a->ldb;
-            tile_stride(l.t.tiled, a->ldb, l.t.n_rows, 4 * l.chunks, &l.q.bts, &l.q.brs);
+            extra_stride(l, a->ldb, &l.q.bts, &l.q.brs);
         }
     }
     return DL_OK;
@@ -460,148 +513,73 @@ int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void 
 
 int shape_cheb_round(const dl_cheb_round_args *a, int n_cus, const Knobs &k, void *ws,
                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
-    // the Chebyshev round's own checks around the round's (y == x allowed, y == z below)
     if (!a) return fail(err, DL_ERR_INVALID, "dl_cheb_round: args is NULL");
     const dl_mix_args &m = a->mix;
     if (!m.x || !m.y || !a->z) return fail(err, DL_ERR_INVALID, "dl_cheb_round: null x/y/z");
     if (m.g)
         return fail(err, DL_ERR_INVALID, "dl_cheb_round: g must be NULL (no local step inside the "
                                          "accelerated round)");
-    if (m.halo || m.n_halo != 0 || m.mean_prev || m.colsum_out || m.n_local_src != 0 ||
-        m.n_halo_blocks != 0 || m.partial_rows_out)
-        return fail(err, DL_ERR_UNSUPPORTED,
-                    "dl_cheb_round: no halo rows, partition row sets or lagged deviation (halo, "
-                    "n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks, partial_rows_out "
-                    "must be NULL / 0)");
-    int rc = check_mix_args(&m, err, true);
+    const Operand z{a->z, a->ldz};
+    const FusedRound r{"dl_cheb_round", "Chebyshev", kLaunchChebTile, &z, 1};
+    int rc = whole_round(r, m, err);
     if (rc) return rc;
-    const bool tiled = m.tile_cols > 0;
-    const int64_t n = m.W.n_rows;
-    if (tiled ? a->ldz < 0 || (a->ldz > 0 && a->ldz < n) || a->ldz > 65535 * 4
-              : a->ldz < m.n_params)
+    const Layout lay(m);
+    if (lay.bad_ld(a->ldz))
         return fail(err, DL_ERR_INVALID, "dl_cheb_round: z laid out as x (row-major ldz >= "
                                          "n_params; column-tiled ldz 0 or >= n_rows)");
-    {
-        const int64_t Tc = m.tile_cols;
-        const int64_t ntl = tiled ? (m.n_params + Tc - 1) / Tc : 0;
-        auto extent = [&](int64_t ld) {
-            return tiled ? (size_t)(((ntl - 1) * (ld ? ld : n) + n) * Tc * 4)
-                         : ((size_t)(n - 1) * ld + m.n_params) * 4;
-        };
-        const bool y_is_z = m.y == a->z && m.ldy == a->ldz;
-        if (!y_is_z && overlaps(a->z, extent(a->ldz), m.y, extent(m.ldy)))
-            return fail(err, DL_ERR_INVALID, "dl_cheb_round: y overlaps z (y may be z itself "
-                                             "with ldy == ldz)");
-    }
-    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_cheb_round_plan: plan is NULL");
-    Plan pl;
-    rc = plan_mix(m, n_cus, k, &pl, err);
-    if (rc) return rc;
-    if (pl.pub.path != 1)
-        return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_round: the fused Chebyshev round runs on the "
-                                             "LDS tile kernel (plan path 1); this round plans "
-                                             "path %d", pl.pub.path);
-    if (plan) *plan = pl.pub;
-    if (!out) return DL_OK;
-    // do the float4 kernels reach z: 16-byte aligned, and row-major rows too, within the 32-bit
-    // offsets of a tile base (as tile_args asks of x and y)
-    const bool z_vec = aligned16(a->z) &&
-                       (tiled || (a->ldz % 4 == 0 &&
-                                  ((n - 1) * a->ldz + 128) * 4 < ((int64_t)1 << 32)));
-    rc = shape_round(m, n_cus, k, ws, ws_bytes, out, err, z_vec);
-    if (rc) return rc;
+    const bool y_is_z = m.y == a->z && m.ldy == a->ldz;
+    if (!y_is_z && overlaps(a->z, lay.span(a->ldz), m.y, lay.span(m.ldy)))
+        return fail(err, DL_ERR_INVALID, "dl_cheb_round: y overlaps z (y may be z itself "
+                                         "with ldy == ldz)");
+    rc = plan_and_shape(r, m, n_cus, k, ws, ws_bytes, plan, out, err);
+    if (rc || !out) return rc;
     for (int i = 0; i < out->n; ++i) {
         Launch &l = out->l[i];
-        if (l.kind != kLaunchTile)
-            return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_round: the fused Chebyshev round runs on "
-                                                 "the LDS tile kernel (plan path 1) only");
-        l.kind = kLaunchChebTile;
         l.c.z = a->z;
         l.c.ldz = a->ldz;
         l.c.a = a->a;
         l.c.b = a->b;
-        tile_stride(l.t.tiled, a->ldz, l.t.n_rows, 4 * l.chunks, &l.c.zts, &l.c.zrs);
+        extra_stride(l, a->ldz, &l.c.zts, &l.c.zrs);
     }
     return DL_OK;
 }
 
 int shape_track_round(const dl_track_round_args *a, int n_cus, const Knobs &k, void *ws,
                       size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
-    // the tracking round's own checks around the round's (y == x allowed, d_out == d below)
     if (!a) return fail(err, DL_ERR_INVALID, "dl_track_round: args is NULL");
     const dl_mix_args &m = a->mix;
     if (!m.x || !m.y || !a->d || !a->d_out || !m.g || !a->g_old)
         return fail(err, DL_ERR_INVALID, "dl_track_round: null x/y/d/d_out/g/g_old");
-    if (m.halo || m.n_halo != 0 || m.mean_prev || m.colsum_out || m.n_local_src != 0 ||
-        m.n_halo_blocks != 0 || m.partial_rows_out)
-        return fail(err, DL_ERR_UNSUPPORTED,
-                    "dl_track_round: no halo rows, partition row sets or lagged deviation (halo, "
-                    "n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks, partial_rows_out "
-                    "must be NULL / 0)");
-    int rc = check_mix_args(&m, err, true);
+    const Operand extra[] = {{a->d, a->ldd}, {a->d_out, a->lddo}, {a->g_old, a->ldq}};
+    const FusedRound r{"dl_track_round", "gradient-tracking", kLaunchTrackTile, extra, 3};
+    int rc = whole_round(r, m, err);
     if (rc) return rc;
-    const bool tiled = m.tile_cols > 0;
-    const int64_t n = m.W.n_rows;
-    auto bad_ld = [&](int64_t ld) {
-        return tiled ? ld < 0 || (ld > 0 && ld < n) || ld > 65535 * 4 : ld < m.n_params;
-    };
-    if (bad_ld(a->ldd) || bad_ld(a->lddo) || bad_ld(a->ldq))
+    const Layout lay(m);
+    if (lay.bad_ld(a->ldd) || lay.bad_ld(a->lddo) || lay.bad_ld(a->ldq))
         return fail(err, DL_ERR_INVALID, "dl_track_round: d, d_out and g_old laid out as x "
                                          "(row-major ld >= n_params; column-tiled ld 0 or >= "
                                          "n_rows)");
-    {
-        const int64_t Tc = m.tile_cols;
-        const int64_t ntl = tiled ? (m.n_params + Tc - 1) / Tc : 0;
-        auto extent = [&](int64_t ld) {
-            return tiled ? (size_t)(((ntl - 1) * (ld ? ld : n) + n) * Tc * 4)
-                         : ((size_t)(n - 1) * ld + m.n_params) * 4;
-        };
-        const size_t dob = extent(a->lddo), yb = extent(m.ldy);
-        const bool in_place = a->d_out == a->d && a->lddo == a->ldd;
-        if (!in_place && overlaps(a->d_out, dob, a->d, extent(a->ldd)))
-            return fail(err, DL_ERR_INVALID, "dl_track_round: d_out overlaps d (d_out may be d "
-                                             "itself with lddo == ldd)");
-        const Span in[] = {{m.x, extent(m.ldx)}, {m.y, yb}, {m.g, extent(m.ldg)},
-                           {a->g_old, extent(a->ldq)}};
-        const char *const in_name[] = {"x", "y", "g", "g_old"};
-        const Span od{a->d_out, dob};
-        const char *const od_name = "d_out";
-        rc = check_disjoint("dl_track_round", &od, &od_name, 1, in, in_name, 4, err);
-        if (rc) return rc;
-        // (y against x and g: check_mix_args)
-        const Span yin[] = {{a->d, extent(a->ldd)}, {a->g_old, extent(a->ldq)}};
-        const char *const yin_name[] = {"d", "g_old"};
-        const Span oy{m.y, yb};
-        const char *const oy_name = "y";
-        rc = check_disjoint("dl_track_round", &oy, &oy_name, 1, yin, yin_name, 2, err);
-        if (rc) return rc;
-    }
-    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_track_round_plan: plan is NULL");
-    Plan pl;
-    rc = plan_mix(m, n_cus, k, &pl, err);
+    const Span d{a->d, lay.span(a->ldd)}, d_out{a->d_out, lay.span(a->lddo)};
+    const Span y{m.y, lay.span(m.ldy)}, g_old{a->g_old, lay.span(a->ldq)};
+    const bool in_place = a->d_out == a->d && a->lddo == a->ldd;
+    if (!in_place && overlaps(d_out.p, d_out.n, d.p, d.n))
+        return fail(err, DL_ERR_INVALID, "dl_track_round: d_out overlaps d (d_out may be d "
+                                         "itself with lddo == ldd)");
+    const Span in[] = {{m.x, lay.span(m.ldx)}, y, {m.g, lay.span(m.ldg)}, g_old};
+    const char *const in_name[] = {"x", "y", "g", "g_old"};
+    const char *const d_out_name = "d_out";
+    rc = check_disjoint(r.name, &d_out, &d_out_name, 1, in, in_name, 4, err);
     if (rc) return rc;
-    if (pl.pub.path != 1)
-        return fail(err, DL_ERR_UNSUPPORTED, "dl_track_round: the fused gradient-tracking round "
-                                             "runs on the LDS tile kernel (plan path 1); this "
-                                             "round plans path %d", pl.pub.path);
-    if (plan) *plan = pl.pub;
-    if (!out) return DL_OK;
-    // do the float4 kernels reach d, d_out and g_old: 16-byte aligned, and row-major rows too,
-    // within the 32-bit offsets of a tile base (as tile_args asks of x, g and y)
-    auto reach = [&](const void *p, int64_t ld) {
-        return aligned16(p) &&
-               (tiled || (ld % 4 == 0 && ((n - 1) * ld + 128) * 4 < ((int64_t)1 << 32)));
-    };
-    rc = shape_round(m, n_cus, k, ws, ws_bytes, out, err,
-                     reach(a->d, a->ldd) && reach(a->d_out, a->lddo) && reach(a->g_old, a->ldq));
+    // (y against x and g: check_mix_args)
+    const Span yin[] = {d, g_old};
+    const char *const yin_name[] = {"d", "g_old"};
+    const char *const y_name = "y";
+    rc = check_disjoint(r.name, &y, &y_name, 1, yin, yin_name, 2, err);
     if (rc) return rc;
+    rc = plan_and_shape(r, m, n_cus, k, ws, ws_bytes, plan, out, err);
+    if (rc || !out) return rc;
     for (int i = 0; i < out->n; ++i) {
         Launch &l = out->l[i];
-        if (l.kind != kLaunchTile)
-            return fail(err, DL_ERR_UNSUPPORTED, "dl_track_round: the fused gradient-tracking "
-                                                 "round runs on the LDS tile kernel (plan path 1) "
-                                                 "only");
-        l.kind = kLaunchTrackTile;
         TrackTileArgs &q = l.k;
         q.d = a->d;
         q.ldd = a->ldd;
@@ -609,10 +587,9 @@ int shape_track_round(const dl_track_round_args *a, int n_cus, const Knobs &k, v
         q.lddo = a->lddo;
         q.q = a->g_old;
         q.ldq = a->ldq;
-        const int64_t T = 4 * l.chunks;
-        tile_stride(l.t.tiled, a->ldd, l.t.n_rows, T, &q.dts, &q.drs);
-        tile_stride(l.t.tiled, a->lddo, l.t.n_rows, T, &q.dots, &q.dors);
-        tile_stride(l.t.tiled, a->ldq, l.t.n_rows, T, &q.qts, &q.qrs);
+        extra_stride(l, a->ldd, &q.dts, &q.drs);
+        extra_stride(l, a->lddo, &q.dots, &q.dors);
+        extra_stride(l, a->ldq, &q.qts, &q.qrs);
     }
     return DL_OK;
 }

@@ -203,26 +203,21 @@ void tile_stride(bool tiled, int64_t ld, int64_t rows, int64_t T, int64_t *ts, u
 // the float4 kernels out
 int shape_round(const dl_mix_args &a, int n_cus, const Knobs &k, void *ws, size_t ws_bytes,
                 Launches *out, char *err, bool vec_ok = true);
-// dl_sgd_round / dl_sgd_round_plan, in the header's order: the round's own checks (with y == x
-// allowed) and the momentum buffer's, the plan (refused unless path 1; copied to *plan when
-// given), then shape_round with the float4 kernels ruled out when they cannot reach the buffers,
-// every launch a kLaunchSgdTile with its SgdTileArgs.  out NULL: the plan query, which stops
-// after the plan and needs `plan`.
+// The fused rounds (dl_X_round / dl_X_round_plan), one sequence in the header's order: the
+// entry point's own null checks, whole rounds only (no halo, partition or lagged field) and the
+// round's checks with y == x allowed, the layouts and overlaps of the operands the round adds,
+// the plan (refused unless path 1; copied to *plan when given), then shape_round with the float4
+// kernels ruled out when they cannot reach an added operand, every launch re-tagged with the
+// round's kind and given its extra args.  out NULL: the plan query, which stops after the plan
+// and needs `plan`.  What each adds:
+// momentum buffers when momentum != 0, the Nesterov rule; kLaunchSgdTile with SgdTileArgs
 int shape_sgd_round(const dl_sgd_round_args *a, int n_cus, const Knobs &k, void *ws,
                     size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
-// dl_cheb_round / dl_cheb_round_plan, in the header's order: the Chebyshev round's own checks (g
-// refused, y == x and y == z allowed) around the round's, z's strides, the plan (refused unless
-// path 1; copied to *plan when given), then shape_round with the float4 kernels ruled out when
-// they cannot reach z, every launch a kLaunchChebTile with its ChebTileArgs.  out NULL: the plan
-// query, which stops after the plan and needs `plan`.
+// z (y may be z itself), g refused before anything else; kLaunchChebTile with ChebTileArgs
 int shape_cheb_round(const dl_cheb_round_args *a, int n_cus, const Knobs &k, void *ws,
                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
-// dl_track_round / dl_track_round_plan, in the header's order: the gradient-tracking round's own
-// checks (y == x and d_out == d allowed, every other overlap of an output refused) around the
-// round's, the layouts of d, d_out and g_old, the plan (refused unless path 1; copied to *plan
-// when given), then shape_round with the float4 kernels ruled out when they cannot reach d,
-// d_out or g_old, every launch a kLaunchTrackTile with its TrackTileArgs.  out NULL: the plan
-// query, which stops after the plan and needs `plan`.
+// d, d_out (may be d itself) and g_old, every other overlap of an output refused;
+// kLaunchTrackTile with TrackTileArgs
 int shape_track_round(const dl_track_round_args *a, int n_cus, const Knobs &k, void *ws,
                       size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,

@@ -266,22 +266,62 @@ def mix_rounds(W: DeviceCsr, X, Y, rounds, G=None, lr=0.0, dev_sq=None, dev_max=
     return True
 
 
-def _sgd_round_args(W, X, Y, G, M, lr, momentum, dampening, weight_decay, nesterov, first,
-                    dev_sq, dev_max, mean, tiled):
+def _fused_round_operands(who, missing, W, X, Y, G, lr, dev_sq, dev_max, mean, tiled, extras):
+    """What the fused rounds' argument structs share: whole rounds only, then ``missing`` (the
+    round's text for an operand it needs and did not get, or None), the round's dl_mix_args, and
+    the leading dimension of every extra operand ``(name, tensor)``, checked to be laid out as X
+    (0 for a tensor that is None)."""
     if W.n_src != W.n_rows or W.n_local != W.n_rows:
-        raise ValueError("sgd_round mixes whole rounds only (no halo rows, no partition row set)")
-    if G is None:
-        raise ValueError("sgd_round needs the gradients G")
-    if momentum != 0.0 and M is None:
-        raise ValueError("momentum needs a buffer M")
+        raise ValueError(f"{who} mixes whole rounds only (no halo rows, no partition row set)")
+    if missing:
+        raise ValueError(missing)
     if tiled is not None:
         mix = mix_args_tiled(W, tiled[0], tiled[1], X, Y, G, lr, dev_sq, dev_max, mean)
-        ldb = _tiled_ld(M, "M", W.n_rows, tiled[0], tiled[1], W.device) if M is not None else 0
+        lds = [_tiled_ld(t, name, W.n_rows, tiled[0], tiled[1], W.device) if t is not None else 0
+               for name, t in extras]
     else:
         mix = mix_args(W, X, Y, G, lr, None, dev_sq, dev_max, mean)
-        if M is not None:
-            _check(M, "M", W.n_rows, X.shape[1], W.device)
-        ldb = _ld(M) if M is not None else 0
+        for name, t in extras:
+            if t is not None:
+                _check(t, name, W.n_rows, X.shape[1], W.device)
+        lds = [_ld(t) if t is not None else 0 for _, t in extras]
+    return mix, lds
+
+
+def _fused_round_plan(entry, make_args, W, deviation):
+    """A fused round's plan query ``entry``: ``make_args(dev_sq, dev_max)`` builds its argument
+    struct (a dummy deviation tensor stands for both outputs).  The plan's fields, or None when
+    the round is refused as unsupported."""
+    lib = _lib.load()
+    dummy = torch.empty(1, dtype=torch.float32, device=W.device) if deviation else None
+    args = make_args(dummy, dummy)
+    plan = _lib.DlMixPlan()
+    rc = getattr(lib, entry)(ctypes.byref(args), ctypes.byref(plan))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, entry)
+    return {f: getattr(plan, f) for f, _ in plan._fields_}
+
+
+def _fused_round_run(entry, args, W, n_params, workspace):
+    """Launches the fused round ``entry`` on the current stream; False, launching nothing, when
+    it is refused as unsupported."""
+    lib = _lib.load()
+    workspace = workspace or Workspace(W.device)
+    wp, wn = workspace.ptr_size(lib.dl_mix_workspace_bytes(W.n_rows, 0, n_params))
+    rc = getattr(lib, entry)(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc, entry)
+    return True
+
+
+def _sgd_round_args(W, X, Y, G, M, lr, momentum, dampening, weight_decay, nesterov, first,
+                    dev_sq, dev_max, mean, tiled):
+    missing = ("sgd_round needs the gradients G" if G is None else
+               "momentum needs a buffer M" if momentum != 0.0 and M is None else None)
+    mix, (ldb,) = _fused_round_operands("sgd_round", missing, W, X, Y, G, lr, dev_sq, dev_max,
+                                        mean, tiled, (("M", M),))
     return _lib.DlSgdRoundArgs(mix, _lib.ptr(M), ldb, float(momentum), float(dampening),
                                float(weight_decay), int(bool(nesterov)), int(bool(first)))
 
@@ -290,16 +330,12 @@ def sgd_round_plan(W: DeviceCsr, X, Y, G, M, momentum=0.0, dampening=0.0, weight
                    nesterov=False, deviation=False, tiled=None):
     """dl_sgd_round_plan: the configuration ``sgd_round`` would run for these operands, or None
     when the fused momentum round does not take them (a plan path other than 1)."""
-    lib = _lib.load()
-    dummy = torch.empty(1, dtype=torch.float32, device=W.device) if deviation else None
-    args = _sgd_round_args(W, X, Y, G, M, 0.0, momentum, dampening, weight_decay, nesterov, False,
-                           dummy, dummy, None, tiled)
-    plan = _lib.DlMixPlan()
-    rc = lib.dl_sgd_round_plan(ctypes.byref(args), ctypes.byref(plan))
-    if rc == _lib.DL_ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "dl_sgd_round_plan")
-    return {f: getattr(plan, f) for f, _ in plan._fields_}
+    return _fused_round_plan(
+        "dl_sgd_round_plan",
+        lambda dev_sq, dev_max: _sgd_round_args(W, X, Y, G, M, 0.0, momentum, dampening,
+                                                weight_decay, nesterov, False, dev_sq, dev_max,
+                                                None, tiled),
+        W, deviation)
 
 
 def sgd_round(W: DeviceCsr, X, Y, G, M, lr, momentum=0.0, dampening=0.0, weight_decay=0.0,
@@ -313,46 +349,27 @@ def sgd_round(W: DeviceCsr, X, Y, G, M, lr, momentum=0.0, dampening=0.0, weight_
     ``tiled=(n_params, tile_cols)``: X, G, M, Y in the column-tiled layout.  Returns False,
     launching nothing, when the fused kernel does not take this round (the caller then runs the
     two launches)."""
-    lib = _lib.load()
     P = tiled[0] if tiled is not None else X.shape[1]
     args = _sgd_round_args(W, X, Y, G, M, lr, momentum, dampening, weight_decay, nesterov, first,
                            dev_sq, dev_max, mean, tiled)
-    workspace = workspace or Workspace(W.device)
-    wp, wn = workspace.ptr_size(lib.dl_mix_workspace_bytes(W.n_rows, 0, P))
-    rc = lib.dl_sgd_round(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
-    if rc == _lib.DL_ERR_UNSUPPORTED:
-        return False
-    _lib.check(rc, "dl_sgd_round")
-    return True
+    return _fused_round_run("dl_sgd_round", args, W, P, workspace)
 
 
 def _cheb_round_args(W, X, Y, Z, a, b, dev_sq, dev_max, mean, tiled):
-    if W.n_src != W.n_rows or W.n_local != W.n_rows:
-        raise ValueError("cheb_round mixes whole rounds only (no halo rows, no partition row set)")
-    if Z is None:
-        raise ValueError("cheb_round needs the previous iterate Z")
-    if tiled is not None:
-        mix = mix_args_tiled(W, tiled[0], tiled[1], X, Y, None, 0.0, dev_sq, dev_max, mean)
-        ldz = _tiled_ld(Z, "Z", W.n_rows, tiled[0], tiled[1], W.device)
-    else:
-        mix = mix_args(W, X, Y, None, 0.0, None, dev_sq, dev_max, mean)
-        _check(Z, "Z", W.n_rows, X.shape[1], W.device)
-        ldz = _ld(Z)
+    missing = "cheb_round needs the previous iterate Z" if Z is None else None
+    mix, (ldz,) = _fused_round_operands("cheb_round", missing, W, X, Y, None, 0.0, dev_sq,
+                                        dev_max, mean, tiled, (("Z", Z),))
     return _lib.DlChebRoundArgs(mix, _lib.ptr(Z), ldz, float(a), float(b))
 
 
 def cheb_round_plan(W: DeviceCsr, X, Y, Z, deviation=False, tiled=None):
     """dl_cheb_round_plan: the configuration ``cheb_round`` would run for these operands, or None
     when the fused Chebyshev round does not take them (a plan path other than 1)."""
-    lib = _lib.load()
-    dummy = torch.empty(1, dtype=torch.float32, device=W.device) if deviation else None
-    args = _cheb_round_args(W, X, Y, Z, 1.0, 0.0, dummy, dummy, None, tiled)
-    plan = _lib.DlMixPlan()
-    rc = lib.dl_cheb_round_plan(ctypes.byref(args), ctypes.byref(plan))
-    if rc == _lib.DL_ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "dl_cheb_round_plan")
-    return {f: getattr(plan, f) for f, _ in plan._fields_}
+    return _fused_round_plan(
+        "dl_cheb_round_plan",
+        lambda dev_sq, dev_max: _cheb_round_args(W, X, Y, Z, 1.0, 0.0, dev_sq, dev_max, None,
+                                                 tiled),
+        W, deviation)
 
 
 def cheb_round(W: DeviceCsr, X, Y, Z, a, b, dev_sq=None, dev_max=None, mean=None,
@@ -364,33 +381,16 @@ def cheb_round(W: DeviceCsr, X, Y, Z, a, b, dev_sq=None, dev_max=None, mean=None
     X itself.  ``tiled=(n_params, tile_cols)``: X, Z, Y in the column-tiled layout.  Returns
     False, launching nothing, when the fused kernel does not take this round (the caller then
     runs the two launches)."""
-    lib = _lib.load()
     P = tiled[0] if tiled is not None else X.shape[1]
     args = _cheb_round_args(W, X, Y, Z, a, b, dev_sq, dev_max, mean, tiled)
-    workspace = workspace or Workspace(W.device)
-    wp, wn = workspace.ptr_size(lib.dl_mix_workspace_bytes(W.n_rows, 0, P))
-    rc = lib.dl_cheb_round(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
-    if rc == _lib.DL_ERR_UNSUPPORTED:
-        return False
-    _lib.check(rc, "dl_cheb_round")
-    return True
+    return _fused_round_run("dl_cheb_round", args, W, P, workspace)
 
 
 def _track_round_args(W, X, Y, D, Dout, G, Gold, lr, dev_sq, dev_max, mean, tiled):
-    if W.n_src != W.n_rows or W.n_local != W.n_rows:
-        raise ValueError("track_round mixes whole rounds only (no halo rows, no partition row set)")
-    if D is None or Dout is None or G is None or Gold is None:
-        raise ValueError("track_round needs the tracker D, its output Dout and the gradients G, "
-                         "Gold")
-    others = (("D", D), ("Dout", Dout), ("Gold", Gold))
-    if tiled is not None:
-        mix = mix_args_tiled(W, tiled[0], tiled[1], X, Y, G, lr, dev_sq, dev_max, mean)
-        lds = [_tiled_ld(t, name, W.n_rows, tiled[0], tiled[1], W.device) for name, t in others]
-    else:
-        mix = mix_args(W, X, Y, G, lr, None, dev_sq, dev_max, mean)
-        for name, t in others:
-            _check(t, name, W.n_rows, X.shape[1], W.device)
-        lds = [_ld(t) for _, t in others]
+    missing = ("track_round needs the tracker D, its output Dout and the gradients G, Gold"
+               if D is None or Dout is None or G is None or Gold is None else None)
+    mix, lds = _fused_round_operands("track_round", missing, W, X, Y, G, lr, dev_sq, dev_max,
+                                     mean, tiled, (("D", D), ("Dout", Dout), ("Gold", Gold)))
     return _lib.DlTrackRoundArgs(mix, _lib.ptr(D), lds[0], _lib.ptr(Dout), lds[1],
                                  _lib.ptr(Gold), lds[2])
 
@@ -398,15 +398,11 @@ def _track_round_args(W, X, Y, D, Dout, G, Gold, lr, dev_sq, dev_max, mean, tile
 def track_round_plan(W: DeviceCsr, X, Y, D, Dout, G, Gold, deviation=False, tiled=None):
     """dl_track_round_plan: the configuration ``track_round`` would run for these operands, or
     None when the fused gradient-tracking round does not take them (a plan path other than 1)."""
-    lib = _lib.load()
-    dummy = torch.empty(1, dtype=torch.float32, device=W.device) if deviation else None
-    args = _track_round_args(W, X, Y, D, Dout, G, Gold, 0.0, dummy, dummy, None, tiled)
-    plan = _lib.DlMixPlan()
-    rc = lib.dl_track_round_plan(ctypes.byref(args), ctypes.byref(plan))
-    if rc == _lib.DL_ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "dl_track_round_plan")
-    return {f: getattr(plan, f) for f, _ in plan._fields_}
+    return _fused_round_plan(
+        "dl_track_round_plan",
+        lambda dev_sq, dev_max: _track_round_args(W, X, Y, D, Dout, G, Gold, 0.0, dev_sq,
+                                                  dev_max, None, tiled),
+        W, deviation)
 
 
 def track_round(W: DeviceCsr, X, Y, D, Dout, G, Gold, lr, dev_sq=None, dev_max=None, mean=None,
@@ -419,16 +415,9 @@ def track_round(W: DeviceCsr, X, Y, D, Dout, G, Gold, lr, dev_sq=None, dev_max=N
     itself and Y may be X itself.  ``tiled=(n_params, tile_cols)``: every operand in the
     column-tiled layout.  Returns False, launching nothing, when the fused kernel does not take
     this round (the caller then runs the three steps)."""
-    lib = _lib.load()
     P = tiled[0] if tiled is not None else X.shape[1]
     args = _track_round_args(W, X, Y, D, Dout, G, Gold, lr, dev_sq, dev_max, mean, tiled)
-    workspace = workspace or Workspace(W.device)
-    wp, wn = workspace.ptr_size(lib.dl_mix_workspace_bytes(W.n_rows, 0, P))
-    rc = lib.dl_track_round(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
-    if rc == _lib.DL_ERR_UNSUPPORTED:
-        return False
-    _lib.check(rc, "dl_track_round")
-    return True
+    return _fused_round_run("dl_track_round", args, W, P, workspace)
 
 
 def axpby(S, Z, a, b, out=None):
