@@ -110,6 +110,25 @@ class DlTrackRoundArgs(ctypes.Structure):
                 ("g_old", _vp), ("ldq", _i64)]
 
 
+class DlAdamArgs(ctypes.Structure):
+    _fields_ = [("x", _vp), ("ldx", _i64), ("g", _vp), ("ldg", _i64), ("m", _vp), ("ldm", _i64),
+                ("v", _vp), ("ldv", _i64), ("out", _vp), ("ldo", _i64), ("n_rows", _i32),
+                ("n_params", _i64), ("beta1", _f64), ("beta2", _f64), ("lr", _f32), ("eps", _f32),
+                ("weight_decay", _f32), ("decoupled", _i32), ("step_size", _f32),
+                ("bias2_sqrt", _f32), ("coef", _vp)]
+
+
+class DlAdamRoundArgs(ctypes.Structure):
+    _fields_ = [("mix", DlMixArgs), ("m", _vp), ("ldm", _i64), ("v", _vp), ("ldv", _i64),
+                ("beta1", _f64), ("beta2", _f64), ("eps", _f32), ("weight_decay", _f32),
+                ("decoupled", _i32), ("step_size", _f32), ("bias2_sqrt", _f32), ("coef", _vp)]
+
+
+# the device state of dl_adam_tick (include/dlamd.h DL_ADAM_*): indices into a float64[8] tensor
+ADAM_T, ADAM_B1T, ADAM_B2T, ADAM_LR, ADAM_BETA1, ADAM_BETA2, ADAM_COEF = range(7)
+ADAM_STATE_LEN = 8
+
+
 class DlMlpArgs(ctypes.Structure):
     _fields_ = [("n_agents", _i32), ("batch", _i32), ("input_dim", _i32), ("hidden_dim", _i32),
                 ("output_dim", _i32), ("X", _vp), ("ldx", _i64), ("data", _vp), ("s_data", _i64),
@@ -209,6 +228,10 @@ SIGNATURES = {
     "dl_cheb_round": (_i32, [ctypes.POINTER(DlChebRoundArgs), _vp, _sz, _vp]),
     "dl_track_round_plan": (_i32, [ctypes.POINTER(DlTrackRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_track_round": (_i32, [ctypes.POINTER(DlTrackRoundArgs), _vp, _sz, _vp]),
+    "dl_adam_tick": (_i32, [_vp, _vp]),
+    "dl_adam_step": (_i32, [ctypes.POINTER(DlAdamArgs), _vp]),
+    "dl_adam_round_plan": (_i32, [ctypes.POINTER(DlAdamRoundArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_adam_round": (_i32, [ctypes.POINTER(DlAdamRoundArgs), _vp, _sz, _vp]),
     "dl_axpby": (_i32, [_vp, _i64, _vp, _i64, _f32, _f32, _vp, _i64, _i32, _i64, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),

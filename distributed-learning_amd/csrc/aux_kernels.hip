@@ -4,6 +4,7 @@
 //   max column std                (mixer.py:82-84 intent)
 //   boundary-row local step pack  (multi-GPU halo send buffers)
 //   Perron / asyncio Jacobi round (consensus_asyncio.py:231-310), fp32 and fp64
+#include "adam_elem.h"
 #include "dl_internal.h"
 #include "sgd_elem.h"
 
@@ -216,6 +217,72 @@ __global__ void __launch_bounds__(256) sgd_step_kernel(const float *x, int64_t l
             orow[i] = o;
         }
     }
+}
+
+// torch.optim.Adam / AdamW step over a block of agent rows: the element arithmetic is adam_elem
+// (adam_elem.h), m and v are updated in place, out may alias x.  The coefficients are read once
+// per workgroup (AdamParams::coef) or come by value.
+template <bool VEC>
+__global__ void __launch_bounds__(256) adam_step_kernel(const float *x, int64_t ldx,
+                                                        const float *__restrict__ g, int64_t ldg,
+                                                        float *__restrict__ m, int64_t ldm,
+                                                        float *__restrict__ v, int64_t ldv,
+                                                        float *out, int64_t ldo, int64_t n_params,
+                                                        AdamParams p) {
+    const int r = blockIdx.y;
+    const float *xr = x + (int64_t)r * ldx;
+    const float *gr = g + (int64_t)r * ldg;
+    float *mr = m + (int64_t)r * ldm;
+    float *vr = v + (int64_t)r * ldv;
+    float *orow = out + (int64_t)r * ldo;
+    const float ss = adam_step_size(p);
+    const float bs = adam_bias2_sqrt(p);
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    if (VEC) {
+        const int64_t n4 = n_params >> 2;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+            const v4f xv = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(xr) + i);
+            const v4f gv = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(gr) + i);
+            v4f mv = reinterpret_cast<const v4f *>(mr)[i];
+            v4f vv = reinterpret_cast<const v4f *>(vr)[i];
+            v4f ov;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float me = mv[k], ve = vv[k];
+                ov[k] = adam_elem(xv[k], gv[k], me, ve, p, ss, bs);
+                mv[k] = me;
+                vv[k] = ve;
+            }
+            reinterpret_cast<v4f *>(mr)[i] = mv;
+            reinterpret_cast<v4f *>(vr)[i] = vv;
+            reinterpret_cast<v4f *>(orow)[i] = ov;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_params; i += stride) {
+            float me = mr[i], ve = vr[i];
+            const float o = adam_elem(xr[i], gr[i], me, ve, p, ss, bs);
+            mr[i] = me;
+            vr[i] = ve;
+            orow[i] = o;
+        }
+    }
+}
+
+// One Adam step of the device-resident step count (include/dlamd.h DL_ADAM_*): t += 1, the
+// running products beta1^t and beta2^t by one fp64 multiply each (not pow: a Python float loop
+// gives the same bits), then ss = fl32(lr / (1 - beta1^t)) and bs = fl32(sqrt(1 - beta2^t)), both
+// in fp64 with the correctly rounded divide and square root, written as two floats into the
+// state's coefficient slot.  One thread.
+__global__ void __launch_bounds__(64) adam_tick_kernel(double *st) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double b1t = st[DL_ADAM_B1T] * st[DL_ADAM_BETA1];
+    const double b2t = st[DL_ADAM_B2T] * st[DL_ADAM_BETA2];
+    st[DL_ADAM_T] = st[DL_ADAM_T] + 1.0;
+    st[DL_ADAM_B1T] = b1t;
+    st[DL_ADAM_B2T] = b2t;
+    float *coef = reinterpret_cast<float *>(st + DL_ADAM_COEF);
+    coef[0] = (float)(st[DL_ADAM_LR] / (1.0 - b1t));
+    coef[1] = (float)__builtin_sqrt(1.0 - b2t);
 }
 
 // out = fl(fl(a s) + fl(b z)) over a block of agent rows: the Chebyshev round's second line
@@ -472,6 +539,30 @@ hipError_t launch_sgd_step(const float *x, int64_t ldx, const float *g, int64_t 
     else
         hipLaunchKernelGGL(sgd_step_kernel<false>, dim3((unsigned)bx, n_rows), dim3(256), 0, s, x,
                            ldx, g, ldg, buf, ldb, out, ldo, n_params, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_adam_step(const float *x, int64_t ldx, const float *g, int64_t ldg, float *m,
+                            int64_t ldm, float *v, int64_t ldv, float *out, int64_t ldo,
+                            int n_rows, int64_t n_params, const AdamParams &p, bool vec,
+                            hipStream_t s) {
+    const int64_t work = vec ? n_params >> 2 : n_params;
+    int64_t bx = (work + 255) / 256;
+    // ~16 workgroups per CU over all rows, each thread a few float4s (grid-stride)
+    int64_t cap = (8192 + n_rows - 1) / n_rows;
+    if (cap < 1) cap = 1;
+    if (bx > cap) bx = cap;
+    if (vec)
+        hipLaunchKernelGGL(adam_step_kernel<true>, dim3((unsigned)bx, n_rows), dim3(256), 0, s, x,
+                           ldx, g, ldg, m, ldm, v, ldv, out, ldo, n_params, p);
+    else
+        hipLaunchKernelGGL(adam_step_kernel<false>, dim3((unsigned)bx, n_rows), dim3(256), 0, s,
+                           x, ldx, g, ldg, m, ldm, v, ldv, out, ldo, n_params, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_adam_tick(double *state, hipStream_t s) {
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, s, state);
     return hipGetLastError();
 }
 

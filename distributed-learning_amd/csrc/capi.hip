@@ -2,7 +2,7 @@
 // the environment knobs, read once per call.  What an entry point checks and launches is decided
 // by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here their
 // description of a call is turned into launch_* calls and the step after them.  Shaped there:
-// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round), the one-pass
+// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round, dl_adam_round), the one-pass
 // deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch, dl_lenet_grad
 // and dl_lenet_eval.  The others (dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
 // deviation, the conversions, the step-rows functions, ...) check their own arguments here:
@@ -144,6 +144,9 @@ int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, cons
             case dl::kLaunchTrackTile:
                 e = dl::launch_mix_track_tile(l.t, l.k, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
                 break;
+            case dl::kLaunchAdamTile:
+                e = dl::launch_mix_adam_tile(l.t, l.a, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
+                break;
             case dl::kLaunchTileReg:
                 e = dl::launch_mix_tile_reg(l.t, l.chunks, l.head, l.tail_fmt, l.sgd, l.dev, l.grid,
                                             l.lds, s);
@@ -194,7 +197,8 @@ int deviation_one_pass(const float *x, int64_t ldx, int32_t tile_cols, int32_t n
     return run(L, dev_sq, dev_max, nullptr, "dev tile", s);
 }
 
-// The fused rounds' entry points (launch.h shape_sgd_round, shape_cheb_round, shape_track_round):
+// The fused rounds' entry points (launch.h shape_sgd_round, shape_cheb_round, shape_track_round,
+// shape_adam_round):
 // the plan query, and the round itself.  kernel: `run`'s name for a tile launch.
 template <class Args>
 using ShapeFused = int (*)(const Args *, int, const dl::Knobs &, void *, size_t, dl_mix_plan *,
@@ -727,6 +731,64 @@ int dl_track_round_plan(const dl_track_round_args *args, dl_mix_plan *plan) {
 int dl_track_round(const dl_track_round_args *args, void *workspace, size_t ws_bytes,
                    dl_stream_t stream) {
     return fused_round(dl::shape_track_round, "mix_track_tile_kernel", args, workspace, ws_bytes,
+                       stream);
+}
+
+int dl_adam_step(const dl_adam_args *a, dl_stream_t stream) {
+    g_err.clear();
+    if (!a) return fail(DL_ERR_INVALID, "dl_adam_step: null args");
+    if (a->n_rows == 0 || a->n_params == 0) return DL_OK;
+    if (!a->x || !a->g || !a->m || !a->v || !a->out || a->n_rows < 0 || a->n_rows > 65535 ||
+        a->n_params < 0 || a->ldx < a->n_params || a->ldg < a->n_params ||
+        a->ldm < a->n_params || a->ldv < a->n_params || a->ldo < a->n_params)
+        return fail(DL_ERR_INVALID, "dl_adam_step: bad arguments (n_rows %d, n_params %lld)",
+                    a->n_rows, (long long)a->n_params);
+    char err[dl::kErrLen];
+    const int rc = dl::check_adam_params("dl_adam_step", a->beta1, a->beta2, a->eps, a->step_size,
+                                         a->bias2_sqrt, a->coef, err);
+    if (rc) return status(rc, err);
+    const size_t rb = (size_t)a->n_params * sizeof(float);
+    auto span = [&](int64_t ld) { return ((size_t)a->n_rows - 1) * ld * 4 + rb; };
+    if (a->out != a->x && overlaps(a->out, span(a->ldo), a->x, span(a->ldx)))
+        return fail(DL_ERR_INVALID, "dl_adam_step: out must be x itself or not overlap it");
+    // m and v are read and written in place: neither shares a byte with anything else
+    const struct { const void *p; int64_t ld; const char *name; } mv[] = {{a->m, a->ldm, "m"},
+                                                                          {a->v, a->ldv, "v"}},
+        other[] = {{a->x, a->ldx, "x"}, {a->g, a->ldg, "g"}, {a->out, a->ldo, "out"}};
+    for (const auto &o : mv)
+        for (const auto &i : other)
+            if (overlaps(o.p, span(o.ld), i.p, span(i.ld)))
+                return fail(DL_ERR_INVALID, "dl_adam_step: %s overlaps %s", o.name, i.name);
+    if (overlaps(a->m, span(a->ldm), a->v, span(a->ldv)))
+        return fail(DL_ERR_INVALID, "dl_adam_step: m overlaps v");
+    const bool vec = aligned16(a->x) && aligned16(a->g) && aligned16(a->out) && aligned16(a->m) &&
+                     aligned16(a->v) && (a->n_params & 3) == 0 && (a->ldx & 3) == 0 &&
+                     (a->ldg & 3) == 0 && (a->ldo & 3) == 0 && (a->ldm & 3) == 0 &&
+                     (a->ldv & 3) == 0;
+    const dl::AdamParams p = dl::adam_params(a->beta1, a->beta2, a->eps, a->lr, a->weight_decay,
+                                             a->decoupled, a->step_size, a->bias2_sqrt, a->coef);
+    hipError_t e = dl::launch_adam_step(a->x, a->ldx, a->g, a->ldg, a->m, a->ldm, a->v, a->ldv,
+                                        a->out, a->ldo, a->n_rows, a->n_params, p, vec,
+                                        static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DL_OK : hip_fail(e, "adam_step launch");
+}
+
+int dl_adam_tick(double *state, dl_stream_t stream) {
+    g_err.clear();
+    if (!state || (reinterpret_cast<uintptr_t>(state) & 7u))
+        return fail(DL_ERR_INVALID, "dl_adam_tick: state must be an 8-byte aligned device "
+                                    "double[DL_ADAM_STATE_LEN]");
+    hipError_t e = dl::launch_adam_tick(state, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DL_OK : hip_fail(e, "adam_tick launch");
+}
+
+int dl_adam_round_plan(const dl_adam_round_args *args, dl_mix_plan *plan) {
+    return fused_round_plan(dl::shape_adam_round, args, plan);
+}
+
+int dl_adam_round(const dl_adam_round_args *args, void *workspace, size_t ws_bytes,
+                  dl_stream_t stream) {
+    return fused_round(dl::shape_adam_round, "mix_adam_tile_kernel", args, workspace, ws_bytes,
                        stream);
 }
 

@@ -52,6 +52,11 @@ hipError_t launch_mix_cheb_tile(const TileArgs &a, const ChebTileArgs &q, int ch
 // set), plus the tracker, its output and last step's gradient (launch.h TrackTileArgs).
 hipError_t launch_mix_track_tile(const TileArgs &a, const TrackTileArgs &q, int chunks, bool dev,
                                  int grid, int lds_bytes, bool fast, hipStream_t s);
+// The Adam round's tile kernel (mix_adam.hip) for one launch of a path-1 round shaped by
+// shape_adam_round: TileArgs as for launch_mix_tile (g required, no halo rows, no row set), plus
+// the two moments and the optimizer's parameters (launch.h AdamTileArgs).
+hipError_t launch_mix_adam_tile(const TileArgs &a, const AdamTileArgs &q, int chunks, bool dev,
+                                int grid, int lds_bytes, bool fast, hipStream_t s);
 // out = fl(fl(a * s) + fl(b * z)) over n_rows x n_params (aux_kernels.hip); vec: float4 accesses
 hipError_t launch_axpby(const float *src, int64_t lds_, const float *z, int64_t ldz, float a,
                         float b, float *out, int64_t ldo, int n_rows, int64_t n_params, bool vec,
@@ -102,6 +107,13 @@ hipError_t launch_sgd_step(const float *x, int64_t ldx, const float *g, int64_t 
                            int64_t ldb, float *out, int64_t ldo, int n_rows, int64_t n_params,
                            float lr, float mu, float damp, float wd, int first, int nesterov,
                            bool vec, hipStream_t s);
+// adam_elem over n_rows x n_params, m and v in place (aux_kernels.hip); vec: float4 accesses
+hipError_t launch_adam_step(const float *x, int64_t ldx, const float *g, int64_t ldg, float *m,
+                            int64_t ldm, float *v, int64_t ldv, float *out, int64_t ldo,
+                            int n_rows, int64_t n_params, const AdamParams &p, bool vec,
+                            hipStream_t s);
+// one step of the device-resident Adam step count (include/dlamd.h DL_ADAM_*)
+hipError_t launch_adam_tick(double *state, hipStream_t s);
 
 struct PerronArgs {
     void *y;

@@ -594,6 +594,76 @@ int shape_track_round(const dl_track_round_args *a, int n_cus, const Knobs &k, v
     return DL_OK;
 }
 
+AdamParams adam_params(double beta1, double beta2, float eps, float lr, float wd, int decoupled,
+                       float ss, float bs, const float *coef) {
+    AdamParams p;
+    p.b2 = (float)beta2;
+    p.omb1 = (float)(1.0 - beta1);
+    p.omb2 = (float)(1.0 - beta2);
+    p.eps = eps;
+    p.wd = wd;
+    p.decay = (float)(1.0 - (double)lr * (double)wd);
+    p.ss = ss;
+    p.bs = bs;
+    p.decoupled = decoupled ? 1 : 0;
+    p.coef = coef;
+    return p;
+}
+
+int check_adam_params(const char *who, double beta1, double beta2, float eps, float ss, float bs,
+                      const float *coef, char *err) {
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return fail(err, DL_ERR_INVALID, "%s: beta1 and beta2 must be in [0, 1) (got %g, %g)", who,
+                    beta1, beta2);
+    if (!(eps >= 0.f)) return fail(err, DL_ERR_INVALID, "%s: eps must be >= 0", who);
+    // (x - x is 0 for a finite x and NaN otherwise)
+    if (!coef && (ss - ss != 0.f || bs - bs != 0.f))
+        return fail(err, DL_ERR_INVALID, "%s: step_size and bias2_sqrt must be finite when coef "
+                                         "is NULL", who);
+    return DL_OK;
+}
+
+int shape_adam_round(const dl_adam_round_args *a, int n_cus, const Knobs &k, void *ws,
+                     size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_adam_round: args is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y || !m.g || !a->m || !a->v)
+        return fail(err, DL_ERR_INVALID, "dl_adam_round: null x/y/g/m/v");
+    const Operand extra[] = {{a->m, a->ldm}, {a->v, a->ldv}};
+    const FusedRound r{"dl_adam_round", "Adam", kLaunchAdamTile, extra, 2};
+    int rc = whole_round(r, m, err);
+    if (rc) return rc;
+    const Layout lay(m);
+    if (lay.bad_ld(a->ldm) || lay.bad_ld(a->ldv))
+        return fail(err, DL_ERR_INVALID, "dl_adam_round: m and v laid out as x (row-major ld >= "
+                                         "n_params; column-tiled ld 0 or >= n_rows)");
+    rc = check_adam_params(r.name, a->beta1, a->beta2, a->eps, a->step_size, a->bias2_sqrt,
+                           a->coef, err);
+    if (rc) return rc;
+    // m and v are read and written: neither shares a byte with the other or with x, y or g
+    const Span mv[] = {{a->m, lay.span(a->ldm)}, {a->v, lay.span(a->ldv)}};
+    const char *const mv_name[] = {"m", "v"};
+    const Span in[] = {{m.x, lay.span(m.ldx)}, {m.y, lay.span(m.ldy)}, {m.g, lay.span(m.ldg)}};
+    const char *const in_name[] = {"x", "y", "g"};
+    rc = check_disjoint(r.name, mv, mv_name, 2, in, in_name, 3, err);
+    if (rc) return rc;
+    rc = plan_and_shape(r, m, n_cus, k, ws, ws_bytes, plan, out, err);
+    if (rc || !out) return rc;
+    for (int i = 0; i < out->n; ++i) {
+        Launch &l = out->l[i];
+        AdamTileArgs &q = l.a;
+        q.m = a->m;
+        q.ldm = a->ldm;
+        q.v = a->v;
+        q.ldv = a->ldv;
+        extra_stride(l, a->ldm, &q.mts, &q.mrs);
+        extra_stride(l, a->ldv, &q.vts, &q.vrs);
+        q.p = adam_params(a->beta1, a->beta2, a->eps, m.lr, a->weight_decay, a->decoupled,
+                          a->step_size, a->bias2_sqrt, a->coef);
+    }
+    return DL_OK;
+}
+
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err) {
     reset(out);

@@ -3,7 +3,7 @@
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
 // rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round,
-// dl_track_round and their plan queries),
+// dl_track_round, dl_adam_round and their plan queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -145,6 +145,35 @@ struct TrackTileArgs {
     uint32_t drs, dors, qrs;  // FAST-path row strides in bytes
 };
 
+// Adam's element arithmetic (adam_elem.h), shared by dl_adam_step and the fused Adam round: the
+// host-prepared fp32 constants omb1 = fl32(1 - beta1), omb2 = fl32(1 - beta2) and decay = fl32(1 -
+// lr wd), each formed in fp64, and the bias-correction coefficients ss = fl32(lr / (1 - beta1^t))
+// and bs = fl32(sqrt(1 - beta2^t)) -- by value, or when coef != NULL read from coef[0] and
+// coef[1] on the device (dl_adam_tick's outputs).
+struct AdamParams {
+    float b2, omb1, omb2, eps, wd, decay;
+    float ss, bs;
+    int decoupled;
+    const float *coef;
+};
+AdamParams adam_params(double beta1, double beta2, float eps, float lr, float wd, int decoupled,
+                       float ss, float bs, const float *coef);
+// beta1, beta2 in [0, 1), eps >= 0, and finite coefficients when they are passed by value; a
+// text for `who` in err and DL_ERR_INVALID otherwise
+int check_adam_params(const char *who, double beta1, double beta2, float eps, float ss, float bs,
+                      const float *coef, char *err);
+// The Adam round's moments (mix_adam.hip): m and v laid out as x, each read and written in place,
+// with their FAST-path strides (tile_stride).
+struct AdamTileArgs {
+    float *m;
+    int64_t ldm;
+    float *v;
+    int64_t ldv;
+    int64_t mts, vts;    // FAST-path tile strides in bytes
+    uint32_t mrs, vrs;   // FAST-path row strides in bytes
+    AdamParams p;
+};
+
 // One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
 // launch_* functions of dl_internal.h take them.
 enum LaunchKind : int32_t {
@@ -157,6 +186,7 @@ enum LaunchKind : int32_t {
     kLaunchTraceIrr,  // launch_mix_trace_irr(t, head, gm, narrow, rounds, grid, lds, trace): same
     kLaunchChebTile,  // launch_mix_cheb_tile(t, c, chunks, dev, grid, lds, fast)
     kLaunchTrackTile, // launch_mix_track_tile(t, k, chunks, dev, grid, lds, fast)
+    kLaunchAdamTile,  // launch_mix_adam_tile(t, a, chunks, dev, grid, lds, fast)
 };
 struct Launch {
     int32_t kind;
@@ -169,6 +199,7 @@ struct Launch {
     SgdTileArgs q;             // kLaunchSgdTile
     ChebTileArgs c;            // kLaunchChebTile
     TrackTileArgs k;           // kLaunchTrackTile
+    AdamTileArgs a;            // kLaunchAdamTile
 };
 // What follows the launches on the stream.
 enum After : int32_t {
@@ -220,6 +251,10 @@ int shape_cheb_round(const dl_cheb_round_args *a, int n_cus, const Knobs &k, voi
 // kLaunchTrackTile with TrackTileArgs
 int shape_track_round(const dl_track_round_args *a, int n_cus, const Knobs &k, void *ws,
                       size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
+// m and v (each in place), every overlap of either refused, the optimizer's parameter ranges;
+// kLaunchAdamTile with AdamTileArgs
+int shape_adam_round(const dl_adam_round_args *a, int n_cus, const Knobs &k, void *ws,
+                     size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err);
 int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,

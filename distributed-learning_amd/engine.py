@@ -7,6 +7,7 @@ fresh fp32 array per agent and term.  Flattening models to X happens once per ``
 (mixer.py:26), not per round.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -420,6 +421,138 @@ def track_round(W: DeviceCsr, X, Y, D, Dout, G, Gold, lr, dev_sq=None, dev_max=N
     return _fused_round_run("dl_track_round", args, W, P, workspace)
 
 
+class AdamState:
+    """Adam's step count and bias corrections: ``step_size = fl32(lr / (1 - beta1^t))`` and
+    ``bias2_sqrt = fl32(sqrt(1 - beta2^t))``, the powers by one Python-float multiply a step.
+
+    With a ``device`` it owns the float64[8] state tensor of ``dl_adam_tick`` (include/dlamd.h
+    DL_ADAM_*) and ``coef``, a float32 view of the two coefficients the kernels read, so a captured
+    tick + round advances by itself.  The host mirror (``t``, ``step_size``, ``bias2_sqrt``)
+    follows the same recurrence for by-value calls; ``tick()`` advances both, ``advance_host()``
+    the mirror alone (after a graph replay that held the tick)."""
+
+    def __init__(self, lr, betas=(0.9, 0.999), device=None):
+        self.lr = float(lr)
+        self.beta1, self.beta2 = float(betas[0]), float(betas[1])
+        if not (0.0 <= self.beta1 < 1.0 and 0.0 <= self.beta2 < 1.0):
+            raise ValueError(f"betas must be in [0, 1) (got {betas})")
+        self.device = torch.device(device) if device is not None else None
+        self.state = self.coef = None
+        if self.device is not None:
+            self.state = torch.zeros(_lib.ADAM_STATE_LEN, dtype=torch.float64, device=self.device)
+            self.coef = self.state[_lib.ADAM_COEF:_lib.ADAM_COEF + 1].view(torch.float32)
+        self.reset()
+
+    def reset(self):
+        """Back to t = 0 (host and device); lr and betas stay."""
+        self.t, self.b1t, self.b2t = 0, 1.0, 1.0
+        if self.state is not None:
+            init = [0.0, 1.0, 1.0, self.lr, self.beta1, self.beta2, 0.0, 0.0]
+            self.state.copy_(torch.tensor(init, dtype=torch.float64))
+
+    def set_lr(self, lr):
+        """A new lr from the next tick on (a schedule: also between replays of a captured
+        tick)."""
+        self.lr = float(lr)
+        if self.state is not None:
+            self.state[_lib.ADAM_LR] = self.lr
+
+    def advance_host(self):
+        self.t += 1
+        self.b1t *= self.beta1
+        self.b2t *= self.beta2
+
+    def tick(self):
+        """The next step: one dl_adam_tick launch on the current stream (with a device), and the
+        mirror."""
+        if self.state is not None:
+            _lib.check(_lib.load().dl_adam_tick(_lib.ptr(self.state),
+                                                _lib.stream_handle(self.device)), "dl_adam_tick")
+        self.advance_host()
+
+    @property
+    def step_size(self):
+        return np.float32(self.lr / (1.0 - self.b1t))
+
+    @property
+    def bias2_sqrt(self):
+        return np.float32(math.sqrt(1.0 - self.b2t))
+
+
+def _adam_coefs(who, step_size, bias2_sqrt, coef, device):
+    """(step_size, bias2_sqrt, coef pointer) of an Adam call: the device pair ``coef`` (float32
+    [2], e.g. ``AdamState.coef``), or both values."""
+    if coef is not None:
+        if coef.dtype != torch.float32 or coef.numel() < 2 or coef.device != device or \
+                not coef.is_contiguous():
+            raise ValueError(f"{who}: coef must be a contiguous float32 [2] tensor on the device")
+        return 0.0, 0.0, _lib.ptr(coef)
+    if step_size is None or bias2_sqrt is None:
+        raise ValueError(f"{who} needs step_size and bias2_sqrt, or coef")
+    return float(step_size), float(bias2_sqrt), None
+
+
+def adam_step(X, G, M, V, out=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              decoupled=False, step_size=None, bias2_sqrt=None, coef=None):
+    """``dl_adam_step``: torch.optim.Adam.step (``decoupled``: AdamW) over agent rows (X, G, M, V,
+    out: [N, P] row-major device tensors; M and V updated in place; out defaults to X, i.e. in
+    place).  The bias corrections by value (``AdamState.step_size`` / ``bias2_sqrt``) or from the
+    device pair ``coef``; ``lr`` enters only AdamW's decay.  Stream-ordered, no host sync."""
+    out = X if out is None else out
+    for name, t in (("X", X), ("G", G), ("M", M), ("V", V), ("out", out)):
+        if t is None or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or \
+                tuple(t.shape) != tuple(X.shape) or t.device != X.device:
+            raise ValueError(f"{name} must be a row-major float32 [N, P] tensor like X")
+    ss, bs, cp = _adam_coefs("adam_step", step_size, bias2_sqrt, coef, X.device)
+    args = _lib.DlAdamArgs(_lib.ptr(X), X.stride(0), _lib.ptr(G), G.stride(0), _lib.ptr(M),
+                           M.stride(0), _lib.ptr(V), V.stride(0), _lib.ptr(out), out.stride(0),
+                           X.shape[0], X.shape[1], float(betas[0]), float(betas[1]), float(lr),
+                           float(eps), float(weight_decay), int(bool(decoupled)), ss, bs, cp)
+    _lib.check(_lib.load().dl_adam_step(ctypes.byref(args), _lib.stream_handle(X.device)),
+               "dl_adam_step")
+    return out
+
+
+def _adam_round_args(W, X, Y, G, M, V, lr, betas, eps, weight_decay, decoupled, step_size,
+                     bias2_sqrt, coef, dev_sq, dev_max, mean, tiled):
+    missing = ("adam_round needs the gradients G and the moments M, V"
+               if G is None or M is None or V is None else None)
+    mix, lds = _fused_round_operands("adam_round", missing, W, X, Y, G, lr, dev_sq, dev_max,
+                                     mean, tiled, (("M", M), ("V", V)))
+    ss, bs, cp = _adam_coefs("adam_round", step_size, bias2_sqrt, coef, W.device)
+    return _lib.DlAdamRoundArgs(mix, _lib.ptr(M), lds[0], _lib.ptr(V), lds[1], float(betas[0]),
+                                float(betas[1]), float(eps), float(weight_decay),
+                                int(bool(decoupled)), ss, bs, cp)
+
+
+def adam_round_plan(W: DeviceCsr, X, Y, G, M, V, deviation=False, tiled=None):
+    """dl_adam_round_plan: the configuration ``adam_round`` would run for these operands, or None
+    when the fused Adam round does not take them (a plan path other than 1)."""
+    return _fused_round_plan(
+        "dl_adam_round_plan",
+        lambda dev_sq, dev_max: _adam_round_args(W, X, Y, G, M, V, 0.0, (0.9, 0.999), 1e-8, 0.0,
+                                                 False, 1.0, 1.0, None, dev_sq, dev_max, None,
+                                                 tiled),
+        W, deviation)
+
+
+def adam_round(W: DeviceCsr, X, Y, G, M, V, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+               weight_decay=0.0, decoupled=False, step_size=None, bias2_sqrt=None, coef=None,
+               dev_sq=None, dev_max=None, mean=None, workspace: Workspace = None, tiled=None):
+    """One consensus round with the agents' Adam step fused in, on the current stream
+    (dl_adam_round): Y = W adam(X, G, M, V) [+ deviation of Y], M and V updated in the same pass
+    -- torch.optim.Adam.step (``decoupled``: AdamW) of every row, then the mix, bit for bit
+    ``adam_step`` into a scratch followed by ``mix_round`` of it.  Y may be X itself.  M and V
+    are laid out as X.  The bias corrections by value or from the device pair ``coef``, as
+    ``adam_step``.  ``tiled=(n_params, tile_cols)``: every operand in the column-tiled layout.
+    Returns False, launching nothing, when the fused kernel does not take this round (the caller
+    then runs the two launches)."""
+    P = tiled[0] if tiled is not None else X.shape[1]
+    args = _adam_round_args(W, X, Y, G, M, V, lr, betas, eps, weight_decay, decoupled, step_size,
+                            bias2_sqrt, coef, dev_sq, dev_max, mean, tiled)
+    return _fused_round_run("dl_adam_round", args, W, P, workspace)
+
+
 def axpby(S, Z, a, b, out=None):
     """dl_axpby: out = fl(fl(a * S) + fl(b * Z)) over row-major [n, P] tensors (the Chebyshev
     round's second line as a launch of its own).  out may be S or Z; default a new tensor."""
@@ -795,6 +928,13 @@ def staggered_zeros(shape, slot, device):
     return buf[off:off + numel].view(shape)
 
 
+# Whether GossipEngine.round_adam runs the fused dl_adam_round where it plans (path 1) or the
+# composed dl_adam_step + round() everywhere; the bits are the same.  The rule (as for
+# round_track): the fused kernel is the default only once its gain over the composed form has been
+# measured to exceed the spread between repeated medians (scripts/adam_round_probe.py).
+ADAM_ROUND_FUSED = False
+
+
 class GossipEngine:
     """N agents x P params resident in HBM, mixed by a fixed sparse W.
 
@@ -996,6 +1136,68 @@ class GossipEngine:
         self._S.sub_(Gold)
         mix_round(self.W, self._S, self.D, workspace=self.ws, tiled=tiled)
         self.round(G=self.D, lr=lr, deviation=deviation, mean=mean)
+
+    def reset_adam(self, lr=None, betas=None):
+        """Zero Adam's moments ``M`` and ``V`` and its step count (the state ``round_adam`` starts
+        from), allocating them on first use; ``lr`` / ``betas`` given: for that optimizer.  The
+        step count is ``adam``, an ``AdamState`` on this device."""
+        if getattr(self, "M", None) is None:
+            self.M, self.V = self._empty(), self._empty()
+        else:
+            self.M.zero_()
+            self.V.zero_()
+        old = getattr(self, "adam", None)
+        lr = float(lr) if lr is not None else (old.lr if old is not None else 0.0)
+        betas = ((float(betas[0]), float(betas[1])) if betas is not None else
+                 (old.beta1, old.beta2) if old is not None else (0.9, 0.999))
+        if old is None or betas != (old.beta1, old.beta2):
+            self.adam = AdamState(lr, betas, self.device)
+        else:
+            old.lr = lr
+            old.reset()
+
+    def round_adam(self, G, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
+                   deviation=False, mean=None, fused=None):
+        """One round with the agents' torch.optim.Adam step (``decoupled``: AdamW) fused in:
+        X <- W adam(X, G, M, V), M and V updated (``adam_round``).  The engine owns the moments
+        ``M`` and ``V`` (resident layout, zero until the first round) and the step count ``adam``
+        (``reset_adam`` starts over): every call is one ``dl_adam_tick`` and the round reading
+        its coefficients from the device, so a captured call replays as the next step
+        (``adam.advance_host()`` then keeps the host mirror in step).  A changed ``lr`` is written
+        to the device state before the tick; new betas start over.  G is in the resident layout
+        (``layout_like``).  Where the fused kernel does not take the round (plan paths 2, 4, 5)
+        it runs as dl_adam_step into a scratch matrix and ``round(src=scratch)``: the same bits.
+        fused=False runs that composed form everywhere; None: ``ADAM_ROUND_FUSED``.
+        eps must be > 0: the padding of a resident buffer has v = 0."""
+        if not eps > 0.0:
+            raise ValueError("round_adam needs eps > 0 (zero-gradient elements and the tile "
+                             "padding divide by eps alone)")
+        adam = getattr(self, "adam", None)
+        if adam is None or (float(betas[0]), float(betas[1])) != (adam.beta1, adam.beta2):
+            self.reset_adam(lr, betas)
+            adam = self.adam
+        elif adam.lr != float(lr):
+            adam.set_lr(lr)
+        adam.tick()
+        opt = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=decoupled,
+                   coef=adam.coef)
+        tiled = (self.P, self.T) if self.layout == "tiled" else None
+        if fused is None:
+            fused = ADAM_ROUND_FUSED
+        if fused and adam_round(self.W, self.X, self.Y, G, self.M, self.V,
+                                dev_sq=self.dev_sq if deviation else None,
+                                dev_max=self.dev_max if deviation else None, mean=mean,
+                                workspace=self.ws, tiled=tiled, **opt):
+            self.X, self.Y = self.Y, self.X
+            return
+        if getattr(self, "_S", None) is None:
+            self._S = self._empty()
+        # a resident buffer is contiguous and its tile padding is zero (with m = v = 0 and eps > 0
+        # zeros stay zeros under the step), so the tiled layout is stepped as one row of numel
+        # elements
+        flat = (lambda t: t.view(1, -1)) if tiled else (lambda t: t)
+        adam_step(flat(self.X), flat(G), flat(self.M), flat(self.V), out=flat(self._S), **opt)
+        self.round(src=self._S, deviation=deviation, mean=mean)
 
     def mix_chebyshev(self, gamma, times=1, eps=None, on_deviation=None):
         """``Mixer.mix``'s loop with the rounds accelerated by the Chebyshev semi-iteration

@@ -517,10 +517,17 @@ class MLPConsensusSGD:
     differ.  ``G`` and ``G_alt`` then alternate: ``gradients()`` writes the buffer of the current
     parity and ``round()`` passes the other one as last step's gradient; the parity flips with the
     engine's X / Y, so ``capture()`` records one graph per parity as before.  Needs emit="grad"
-    and no momentum / weight_decay."""
+    and no momentum / weight_decay.
+    optimizer="adam": torch.optim.Adam as the agents' optimizer (``GossipEngine.round_adam`` with
+    ``betas``, ``eps`` and ``weight_decay`` as Adam's L2 term; the engine owns the moments and the
+    step count).  The step count lives on the device and every step ticks it, inside a captured
+    graph too, so ``capture()`` needs no eager step first.  Needs emit="grad"; exclusive with
+    ``tracking`` and with momentum / dampening / nesterov.  The default "sgd" is everything
+    above."""
 
     def __init__(self, ann, eng, data, labels, lr, deviation=True, emit="auto", sampler=None,
-                 momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False, tracking=False):
+                 momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False, tracking=False,
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8):
         if eng.layout == "tiled" and ann.path != "fused":
             raise ValueError("the layered gradients read X row-major: use GossipEngine("
                              "layout='rows') or the fused kernel")
@@ -554,12 +561,23 @@ class MLPConsensusSGD:
         if emit not in ("step", "grad") or (emit == "step" and ann.path != "fused"):
             raise ValueError("emit must be 'grad', or 'step' with the fused gradient kernel")
         self.emit = emit
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError(f"optimizer must be 'sgd' or 'adam' (got {optimizer!r})")
+        self.adam = optimizer == "adam"
+        if self.adam and tracking:
+            raise ValueError("optimizer='adam' and tracking=True are exclusive: gradient tracking "
+                             "steps along the tracker with the plain step")
+        if self.adam and (momentum != 0.0 or dampening != 0.0 or nesterov or emit != "grad"):
+            raise ValueError("optimizer='adam' needs emit='grad' and takes betas / eps / "
+                             "weight_decay, not momentum / dampening / nesterov")
         self.tracking = bool(tracking)
         if self.tracking and (momentum != 0.0 or weight_decay != 0.0 or emit != "grad"):
             raise ValueError("tracking needs emit='grad' and no momentum / weight_decay")
         self.opt = dict(momentum=float(momentum), dampening=float(dampening),
                         weight_decay=float(weight_decay), nesterov=bool(nesterov))
-        self.optimizer = momentum != 0.0 or weight_decay != 0.0
+        self.optimizer = not self.adam and (momentum != 0.0 or weight_decay != 0.0)
+        self.adam_opt = dict(betas=(float(betas[0]), float(betas[1])), eps=float(eps),
+                             weight_decay=float(weight_decay))
         if self.optimizer and emit != "grad":
             raise ValueError("momentum / weight_decay need emit='grad'")
         self.M = torch.zeros_like(eng.X) if momentum != 0.0 else None
@@ -574,6 +592,8 @@ class MLPConsensusSGD:
         self._gpar = 0
         if self.tracking:
             eng.reset_tracker()
+        if self.adam:
+            eng.reset_adam(self.lr, self.adam_opt["betas"])
         self.graphs = None
         self._torch = torch
 
@@ -648,6 +668,8 @@ class MLPConsensusSGD:
             g_old = self.G if self._gpar else self.G_alt
             self.eng.round_track(self._g_now(), g_old, self.lr, deviation=self.deviation)
             self._gpar ^= 1
+        elif self.adam:
+            self.eng.round_adam(self.G, self.lr, deviation=self.deviation, **self.adam_opt)
         elif self.optimizer:
             self.eng.round_sgd(self.G, self.M, self.lr, first=self.steps_done == 0,
                                deviation=self.deviation, **self.opt)
@@ -672,6 +694,8 @@ class MLPConsensusSGD:
                                "momentum SGD differs from the ones a graph replays")
         self.eng.reserve_workspace(self.deviation)
         done = self.steps_done
+        # (recording a step advances the host mirror of Adam's step count, not the device's)
+        adam_host = (self.eng.adam.t, self.eng.adam.b1t, self.eng.adam.b2t) if self.adam else None
         graphs = []
         for _ in range(2):
             g = torch.cuda.CUDAGraph()
@@ -681,6 +705,8 @@ class MLPConsensusSGD:
         self.graphs = graphs              # two swaps: eng.X is the original buffer again
         self._parity = 0
         self.steps_done = done
+        if self.adam:
+            self.eng.adam.t, self.eng.adam.b1t, self.eng.adam.b2t = adam_host
 
     def replay(self, steps=1):
         for _ in range(int(steps)):
@@ -689,6 +715,8 @@ class MLPConsensusSGD:
             self.eng.X, self.eng.Y = self.eng.Y, self.eng.X
             if self.tracking:
                 self._gpar ^= 1
+            if self.adam:
+                self.eng.adam.advance_host()
             self.steps_done += 1
 
     def fit(self, epochs, stat_step=None, test=None):

@@ -33,6 +33,8 @@
  *                          Chebyshev semi-iteration with gamma of fast_averaging.find_optimal_weights
  *   dl_track_round      <- (no reference counterpart) the local step and Mixer.mix's round of
  *                          the consensus notebooks with gradient tracking: exact at a constant lr
+ *   dl_adam_step, dl_adam_tick, dl_adam_round <- (no reference counterpart) torch.optim.Adam /
+ *                          AdamW as the agents' optimizer, alone or fused into the round
  *   dl_mlp_eval         <- MasterNode's per-node test statistics (accuracy and loss of every
  *                          node on the shared test_loader, Man_Colab.ipynb cells 21-23) through
  *                          ANNModel.forward (networks/ann_model.py:27-45), all agents at once
@@ -579,6 +581,120 @@ typedef struct dl_track_round_args {
 int dl_track_round_plan(const dl_track_round_args *args, dl_mix_plan *plan);
 int dl_track_round(const dl_track_round_args *args, void *workspace, size_t ws_bytes,
                    dl_stream_t stream);
+/* Adam (no reference counterpart: the reference's loops step with torch.optim.SGD).  The step of
+ * torch.optim.Adam / AdamW (single-tensor form; no amsgrad, no maximize, no tensor lr) over every
+ * agent row, each line ONE separately rounded fp32 operation per fl() -- no fma -- so a numpy fp32
+ * restatement gives the same bits; the square root and the divides are the correctly rounded
+ * ones:
+ *   g  = fl(fl(wd x) + g)                     weight_decay != 0, decoupled == 0   (Adam's L2)
+ *   x  = fl(x decay)                          weight_decay != 0, decoupled != 0   (AdamW)
+ *   m' = fl(m + fl(omb1 fl(g - m)))
+ *   v' = fl(fl(beta2 v) + fl(fl(omb2 g) g))
+ *   den = fl(fl(fl(sqrt(v')) / bias2_sqrt) + eps)
+ *   s  = fl(x - fl(step_size fl(m' / den)))
+ * with the constants omb1 = fl32(1 - beta1), omb2 = fl32(1 - beta2), decay = fl32(1 - lr
+ * weight_decay) formed in fp64 by the library (beta1 and beta2 are doubles so that 1 - beta is
+ * torch's), beta2 = fl32(beta2), and the bias corrections of step t = 1, 2, ...
+ *   step_size = fl32(lr / (1 - beta1^t)),  bias2_sqrt = fl32(sqrt(1 - beta2^t))     (fp64)
+ * There is no first-step flag: m = v = 0 is the first step.  lr enters the arithmetic only
+ * through step_size and decay.
+ *
+ * The coefficients come by value (step_size, bias2_sqrt; coef NULL), or from the device: coef
+ * points at two floats {step_size, bias2_sqrt} that every workgroup reads once with ordinary
+ * loads, and the by-value fields are ignored.  dl_adam_tick keeps them in a caller-owned device
+ * state of DL_ADAM_STATE_LEN doubles (a torch float64 tensor serves):
+ *   [DL_ADAM_T] the step t (0 before the first tick)    [DL_ADAM_B1T], [DL_ADAM_B2T] beta1^t, beta2^t
+ *   [DL_ADAM_LR], [DL_ADAM_BETA1], [DL_ADAM_BETA2]      the caller's lr, beta1, beta2
+ *   [DL_ADAM_COEF]  two floats in the slot's 8 bytes: step_size, then bias2_sqrt
+ *   [7] reserved
+ * The caller initialises {0, 1, 1, lr, beta1, beta2, 0, 0}.  One tick is: t += 1, each running
+ * product times its beta (one fp64 multiply a step, not pow: a Python float loop gives the same
+ * bits), then the two coefficients by the formulas above.  coef = (const float *)(state +
+ * DL_ADAM_COEF).  With dl_adam_tick and dl_adam_round (or dl_adam_step) captured in one hipGraph
+ * every replay is the next Adam step; the host may overwrite [DL_ADAM_LR] between replays (a
+ * schedule without re-capture; an AdamW decay still uses the lr of the captured args).
+ * Additive: callers detect these by the symbols; DLAMD_ABI_VERSION is unchanged. */
+#define DL_ADAM_T 0
+#define DL_ADAM_B1T 1
+#define DL_ADAM_B2T 2
+#define DL_ADAM_LR 3
+#define DL_ADAM_BETA1 4
+#define DL_ADAM_BETA2 5
+#define DL_ADAM_COEF 6
+#define DL_ADAM_STATE_LEN 8
+/* Stream-ordered, one thread.  DL_ERR_INVALID: state NULL or not 8-byte aligned. */
+int dl_adam_tick(double *state, dl_stream_t stream);
+
+/* The Adam step over [n_rows, n_params] row-major operands (row strides as dl_sgd_step's: every
+ * ld >= n_params, n_rows <= 65535).  m and v are updated in place; out may be x itself (in place,
+ * as optimizer.step) or a separate buffer, e.g. the input of the following dl_mix_round.  float4
+ * accesses when every pointer is 16-byte aligned and n_params and every ld are multiples of 4.
+ *   DL_ERR_INVALID: args NULL; a NULL operand, a bad size or stride ("bad arguments"); beta1 or
+ *     beta2 outside [0, 1) ("beta1 and beta2 must be in [0, 1)"); eps < 0 ("eps must be >= 0");
+ *     coef NULL and a step_size or bias2_sqrt that is not finite ("must be finite when coef is
+ *     NULL"); out overlapping x other than being it; m or v overlapping x, g, out or each other
+ *     ("m overlaps x" ...). */
+typedef struct dl_adam_args {
+    const float *x; int64_t ldx;    /* [n_rows, ldx] parameters */
+    const float *g; int64_t ldg;    /* [n_rows, ldg] gradients */
+    float *m; int64_t ldm;          /* [n_rows, ldm] first moments (exp_avg), in place */
+    float *v; int64_t ldv;          /* [n_rows, ldv] second moments (exp_avg_sq), in place */
+    float *out; int64_t ldo;        /* [n_rows, ldo] stepped parameters (== x or disjoint) */
+    int32_t n_rows;
+    int64_t n_params;
+    double beta1, beta2;
+    float lr;                       /* only in AdamW's decay = 1 - lr weight_decay */
+    float eps, weight_decay;
+    int32_t decoupled;              /* 0: Adam (L2 into the gradient), 1: AdamW */
+    float step_size, bias2_sqrt;    /* by value (coef NULL) */
+    const float *coef;              /* nullable: device {step_size, bias2_sqrt} */
+} dl_adam_args;
+int dl_adam_step(const dl_adam_args *args, dl_stream_t stream);
+
+/* The Adam step above fused into the consensus round that follows it:  y = W adam(x, g, m, v),
+ * m and v updated in the same pass.  Bit for bit dl_adam_step(out = S) followed by
+ * dl_mix_round(x = S, g = NULL), but one launch that moves 28 B per element (read x, g, m, v;
+ * write m', v', y) instead of two that move 36 B, and no scratch matrix S.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   mix.x / mix.y are x / x', mix.g is g (required), mix.lr is the lr of AdamW's decay (the step
+ *     itself takes lr through step_size).  y may be x itself with ldy == ldx (a workgroup stages
+ *     all rows of its columns before it writes them).  m and v are read and written in place.
+ *   m and v are laid out as x: row-major [n_rows, ld >= n_params]; column-tiled (mix.tile_cols >
+ *     0) ld their block rows (0 = n_rows), 16-byte aligned operands.  Row-major: any n_params >=
+ *     1, columns [n_params, ld) of y, m and v are never written.
+ *   dev_sq / dev_max / mean describe y exactly as dl_mix_round's do; workspace
+ *     dl_mix_workspace_bytes.  A doubly stochastic W takes mean(y) as the mean of the staged s;
+ *     a tile whose mean is then not finite is measured in two passes, as for any other W.
+ *   DL_ERR_INVALID: args NULL; x, y, g, m or v NULL ("null x/y/g/m/v"); every argument
+ *     dl_mix_round itself refuses (W's arrays, strides, tile_cols, alignment of tiled operands, y
+ *     overlapping x other than being it, y overlapping g; the texts say dl_mix_round); ldm or ldv
+ *     out of range ("m and v laid out as x"); beta1 or beta2 outside [0, 1) ("beta1 and beta2
+ *     must be in [0, 1)"); eps < 0 ("eps must be >= 0"); coef NULL and a step_size or bias2_sqrt
+ *     that is not finite ("must be finite when coef is NULL"); m or v overlapping x, y, g or each
+ *     other ("m overlaps x", ... "m overlaps v"); dl_adam_round_plan with plan NULL.
+ *   DL_ERR_UNSUPPORTED: any halo, partition or lagged-deviation field (halo, n_halo, mean_prev,
+ *     colsum_out, n_local_src, n_halo_blocks, partial_rows_out); rounds that plan path 2, 4 or 5
+ *     (LDS tile kernel only: the caller runs dl_adam_step + dl_mix_round).
+ *   DL_ERR_WORKSPACE: as dl_mix_round (deviation outputs without a 16-byte aligned workspace of
+ *     dl_mix_workspace_bytes).
+ *   Stream-ordered, no host synchronisation, no allocation: capturable in a hipGraph.
+ * dl_adam_round_plan: DL_OK and the configuration the round would run, or the refusal, without
+ * touching the device. */
+typedef struct dl_adam_round_args {
+    dl_mix_args mix;   /* x, y, W, g (required), lr, n_params, ld*, tile_cols, dev_sq, dev_max, mean;
+                          halo, n_halo, mean_prev, colsum_out, n_local_src, n_halo_blocks,
+                          partial_rows_out must be NULL / 0 */
+    float *m; int64_t ldm;          /* first moments, laid out as x, in place */
+    float *v; int64_t ldv;          /* second moments, laid out as x, in place */
+    double beta1, beta2;
+    float eps, weight_decay;
+    int32_t decoupled;              /* as dl_adam_args */
+    float step_size, bias2_sqrt;    /* by value (coef NULL) */
+    const float *coef;              /* nullable: device {step_size, bias2_sqrt} */
+} dl_adam_round_args;
+int dl_adam_round_plan(const dl_adam_round_args *args, dl_mix_plan *plan);
+int dl_adam_round(const dl_adam_round_args *args, void *workspace, size_t ws_bytes,
+                  dl_stream_t stream);
 /* out[r, j] = fl(fl(a s[r, j]) + fl(b z[r, j])) over n_rows x n_params (row strides lds_, ldz, ldo
  * >= n_params): dl_cheb_round's second line, so dl_mix_round into s and this call give the fused
  * round's bits -- the two-launch form, and the fallback where the round does not plan path 1.  out
