@@ -124,6 +124,10 @@ class DlAdamRoundArgs(ctypes.Structure):
                 ("decoupled", _i32), ("step_size", _f32), ("bias2_sqrt", _f32), ("coef", _vp)]
 
 
+class DlTrimRoundArgs(ctypes.Structure):
+    _fields_ = [("mix", DlMixArgs), ("trim", _i32), ("max_row_nnz", _i32), ("min_row_nnz", _i32)]
+
+
 # the device state of dl_adam_tick (include/dlamd.h DL_ADAM_*): indices into a float64[8] tensor
 ADAM_T, ADAM_B1T, ADAM_B2T, ADAM_LR, ADAM_BETA1, ADAM_BETA2, ADAM_COEF = range(7)
 ADAM_STATE_LEN = 8
@@ -232,6 +236,8 @@ SIGNATURES = {
     "dl_adam_step": (_i32, [ctypes.POINTER(DlAdamArgs), _vp]),
     "dl_adam_round_plan": (_i32, [ctypes.POINTER(DlAdamRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_adam_round": (_i32, [ctypes.POINTER(DlAdamRoundArgs), _vp, _sz, _vp]),
+    "dl_trim_round_plan": (_i32, [ctypes.POINTER(DlTrimRoundArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_trim_round": (_i32, [ctypes.POINTER(DlTrimRoundArgs), _vp, _sz, _vp]),
     "dl_axpby": (_i32, [_vp, _i64, _vp, _i64, _f32, _f32, _vp, _i64, _i32, _i64, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),

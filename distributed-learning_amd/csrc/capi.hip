@@ -2,7 +2,7 @@
 // the environment knobs, read once per call.  What an entry point checks and launches is decided
 // by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here their
 // description of a call is turned into launch_* calls and the step after them.  Shaped there:
-// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round, dl_adam_round), the one-pass
+// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round, dl_adam_round, dl_trim_round), the one-pass
 // deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch, dl_lenet_grad
 // and dl_lenet_eval.  The others (dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
 // deviation, the conversions, the step-rows functions, ...) check their own arguments here:
@@ -147,6 +147,9 @@ int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, cons
             case dl::kLaunchAdamTile:
                 e = dl::launch_mix_adam_tile(l.t, l.a, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
                 break;
+            case dl::kLaunchTrimTile:
+                e = dl::launch_mix_trim_tile(l.t, l.r, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
+                break;
             case dl::kLaunchTileReg:
                 e = dl::launch_mix_tile_reg(l.t, l.chunks, l.head, l.tail_fmt, l.sgd, l.dev, l.grid,
                                             l.lds, s);
@@ -198,7 +201,7 @@ int deviation_one_pass(const float *x, int64_t ldx, int32_t tile_cols, int32_t n
 }
 
 // The fused rounds' entry points (launch.h shape_sgd_round, shape_cheb_round, shape_track_round,
-// shape_adam_round):
+// shape_adam_round, shape_trim_round):
 // the plan query, and the round itself.  kernel: `run`'s name for a tile launch.
 template <class Args>
 using ShapeFused = int (*)(const Args *, int, const dl::Knobs &, void *, size_t, dl_mix_plan *,
@@ -731,6 +734,16 @@ int dl_track_round_plan(const dl_track_round_args *args, dl_mix_plan *plan) {
 int dl_track_round(const dl_track_round_args *args, void *workspace, size_t ws_bytes,
                    dl_stream_t stream) {
     return fused_round(dl::shape_track_round, "mix_track_tile_kernel", args, workspace, ws_bytes,
+                       stream);
+}
+
+int dl_trim_round_plan(const dl_trim_round_args *args, dl_mix_plan *plan) {
+    return fused_round_plan(dl::shape_trim_round, args, plan);
+}
+
+int dl_trim_round(const dl_trim_round_args *args, void *workspace, size_t ws_bytes,
+                  dl_stream_t stream) {
+    return fused_round(dl::shape_trim_round, "mix_trim_tile_kernel", args, workspace, ws_bytes,
                        stream);
 }
 

@@ -57,6 +57,11 @@ hipError_t launch_mix_track_tile(const TileArgs &a, const TrackTileArgs &q, int 
 // the two moments and the optimizer's parameters (launch.h AdamTileArgs).
 hipError_t launch_mix_adam_tile(const TileArgs &a, const AdamTileArgs &q, int chunks, bool dev,
                                 int grid, int lds_bytes, bool fast, hipStream_t s);
+// The trimmed-mean round's tile kernel (mix_trim.hip) for one launch of a path-1 round shaped by
+// shape_trim_round: TileArgs as for launch_mix_tile (g optional, no halo rows, no row set; the
+// weights are not read), plus the trim and the row-length promises (launch.h TrimTileArgs).
+hipError_t launch_mix_trim_tile(const TileArgs &a, const TrimTileArgs &q, int chunks, bool dev,
+                                int grid, int lds_bytes, bool fast, hipStream_t s);
 // out = fl(fl(a * s) + fl(b * z)) over n_rows x n_params (aux_kernels.hip); vec: float4 accesses
 hipError_t launch_axpby(const float *src, int64_t lds_, const float *z, int64_t ldz, float a,
                         float b, float *out, int64_t ldo, int n_rows, int64_t n_params, bool vec,

@@ -664,6 +664,45 @@ int shape_adam_round(const dl_adam_round_args *a, int n_cus, const Knobs &k, voi
     return DL_OK;
 }
 
+int shape_trim_round(const dl_trim_round_args *a, int n_cus, const Knobs &k, void *ws,
+                     size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_trim_round: args is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y) return fail(err, DL_ERR_INVALID, "dl_trim_round: null x/y");
+    if (a->trim < 0 || a->trim > 7)
+        return fail(err, DL_ERR_INVALID, "dl_trim_round: trim must be in 0..7 (got %d)", a->trim);
+    if (a->max_row_nnz < 2 || a->max_row_nnz > 17)
+        return fail(err, DL_ERR_INVALID, "dl_trim_round: max_row_nnz must be in 2..17 (self and "
+                                         "at most 16 neighbours; got %d)", a->max_row_nnz);
+    if (a->max_row_nnz < a->min_row_nnz)
+        return fail(err, DL_ERR_INVALID, "dl_trim_round: max_row_nnz %d below min_row_nnz %d",
+                    a->max_row_nnz, a->min_row_nnz);
+    // trim b needs 2b + 1 neighbours and the self entry; b = 0 the self entry alone
+    const int32_t need = a->trim >= 1 ? 2 * a->trim + 2 : 1;
+    if (a->min_row_nnz < need)
+        return fail(err, DL_ERR_INVALID, "dl_trim_round: trim %d needs min_row_nnz >= %d (got %d)",
+                    a->trim, need, a->min_row_nnz);
+    const int32_t uni = m.W.uniform_row_nnz;
+    if (uni > 0 && (uni > a->max_row_nnz || uni < a->min_row_nnz))
+        return fail(err, DL_ERR_INVALID, "dl_trim_round: uniform_row_nnz %d contradicts the "
+                                         "promised row lengths %d..%d", uni, a->min_row_nnz,
+                    a->max_row_nnz);
+    const FusedRound r{"dl_trim_round", "trimmed-mean", kLaunchTrimTile, nullptr, 0};
+    int rc = whole_round(r, m, err);
+    if (rc) return rc;
+    rc = plan_and_shape(r, m, n_cus, k, ws, ws_bytes, plan, out, err);
+    if (rc || !out) return rc;
+    for (int i = 0; i < out->n; ++i) {
+        Launch &l = out->l[i];
+        // a trimmed mean does not preserve the column mean: always the two-pass deviation
+        l.t.mean_from_inputs = 0;
+        l.r.b = a->trim;
+        l.r.max_nbrs = a->max_row_nnz - 1;
+        l.r.uniform_nbrs = uni > 0 ? uni - 1 : 0;
+    }
+    return DL_OK;
+}
+
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err) {
     reset(out);

@@ -3,7 +3,7 @@
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
 // rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round,
-// dl_track_round, dl_adam_round and their plan queries),
+// dl_track_round, dl_adam_round, dl_trim_round and their plan queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -174,6 +174,15 @@ struct AdamTileArgs {
     AdamParams p;
 };
 
+// The trimmed-mean round's rule (mix_trim.hip): the trim b, the promised longest row's neighbours
+// (entries less the self entry; picks the sorting network) and, for a regular graph, every row's
+// neighbour count (0: read per row).
+struct TrimTileArgs {
+    int32_t b;
+    int32_t max_nbrs;
+    int32_t uniform_nbrs;
+};
+
 // One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
 // launch_* functions of dl_internal.h take them.
 enum LaunchKind : int32_t {
@@ -187,6 +196,7 @@ enum LaunchKind : int32_t {
     kLaunchChebTile,  // launch_mix_cheb_tile(t, c, chunks, dev, grid, lds, fast)
     kLaunchTrackTile, // launch_mix_track_tile(t, k, chunks, dev, grid, lds, fast)
     kLaunchAdamTile,  // launch_mix_adam_tile(t, a, chunks, dev, grid, lds, fast)
+    kLaunchTrimTile,  // launch_mix_trim_tile(t, r, chunks, dev, grid, lds, fast)
 };
 struct Launch {
     int32_t kind;
@@ -200,6 +210,7 @@ struct Launch {
     ChebTileArgs c;            // kLaunchChebTile
     TrackTileArgs k;           // kLaunchTrackTile
     AdamTileArgs a;            // kLaunchAdamTile
+    TrimTileArgs r;            // kLaunchTrimTile
 };
 // What follows the launches on the stream.
 enum After : int32_t {
@@ -254,6 +265,10 @@ int shape_track_round(const dl_track_round_args *a, int n_cus, const Knobs &k, v
 // m and v (each in place), every overlap of either refused, the optimizer's parameter ranges;
 // kLaunchAdamTile with AdamTileArgs
 int shape_adam_round(const dl_adam_round_args *a, int n_cus, const Knobs &k, void *ws,
+                     size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
+// no operand added (g optional): the trim and the two row-length promises, checked against each
+// other and uniform_row_nnz; mean_from_inputs cleared; kLaunchTrimTile with TrimTileArgs
+int shape_trim_round(const dl_trim_round_args *a, int n_cus, const Knobs &k, void *ws,
                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err);

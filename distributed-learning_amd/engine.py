@@ -38,6 +38,22 @@ class DeviceCsr:
         self.shared_row_weights = int(csr.shared_row_weights)
         self.min_row_nnz = csr.min_row_nnz
         self.hub_rows = 0       # dl_mix_args.n_hub_rows (plan path 5 hint; GossipEngine sets it)
+        self._trim = None       # trim_promises(), checked once
+
+    def trim_promises(self):
+        """(max_row_nnz, min_row_nnz) of dl_trim_round_args from the host CSR, after checking --
+        in numpy, once per DeviceCsr -- that every row has exactly one diagonal entry."""
+        if self._trim is None:
+            rp, col = np.asarray(self.csr.rowptr, np.int64), np.asarray(self.csr.col, np.int64)
+            row = np.repeat(np.arange(self.n_rows), np.diff(rp))
+            diag = np.bincount(row[col == row], minlength=self.n_rows)
+            bad = np.flatnonzero(diag != 1)
+            if bad.size:
+                raise ValueError(f"trim_round needs exactly one diagonal entry in every row of W: "
+                                 f"row {int(bad[0])} has {int(diag[bad[0]])}")
+            nnz = np.diff(rp)
+            self._trim = (int(nnz.max()), int(nnz.min()))
+        return self._trim
 
     def c_struct(self):
         return _lib.DlCsr(_lib.ptr(self.rowptr), _lib.ptr(self.col), _lib.ptr(self.w),
@@ -419,6 +435,48 @@ def track_round(W: DeviceCsr, X, Y, D, Dout, G, Gold, lr, dev_sq=None, dev_max=N
     P = tiled[0] if tiled is not None else X.shape[1]
     args = _track_round_args(W, X, Y, D, Dout, G, Gold, lr, dev_sq, dev_max, mean, tiled)
     return _fused_round_run("dl_track_round", args, W, P, workspace)
+
+
+def _trim_round_args(W, X, Y, G, lr, trim, dev_sq, dev_max, mean, tiled):
+    mix, _ = _fused_round_operands("trim_round", None, W, X, Y, G, lr, dev_sq, dev_max, mean,
+                                   tiled, ())
+    hi, lo = W.trim_promises()
+    trim = int(trim)
+    if trim >= 1 and lo < 2 * trim + 2:
+        nnz = np.diff(np.asarray(W.csr.rowptr, np.int64))
+        bad = int(np.flatnonzero(nnz < 2 * trim + 2)[0])
+        raise ValueError(f"trim_round with trim {trim} needs {2 * trim + 1} neighbours in every "
+                         f"row: row {bad} has {int(nnz[bad]) - 1}")
+    if hi > 17:
+        bad = int(np.argmax(np.diff(np.asarray(W.csr.rowptr, np.int64)) > 17))
+        raise ValueError(f"trim_round takes at most 16 neighbours a row: row {bad} has more")
+    # (a graph of isolated agents: the promise only bounds the rows from above)
+    return _lib.DlTrimRoundArgs(mix, trim, max(hi, 2), lo)
+
+
+def trim_round_plan(W: DeviceCsr, X, Y, G=None, trim=1, deviation=False, tiled=None):
+    """dl_trim_round_plan: the configuration ``trim_round`` would run for these operands, or None
+    when the trimmed-mean round does not take them (a plan path other than 1)."""
+    return _fused_round_plan(
+        "dl_trim_round_plan",
+        lambda dev_sq, dev_max: _trim_round_args(W, X, Y, G, 0.0, trim, dev_sq, dev_max, None,
+                                                 tiled),
+        W, deviation)
+
+
+def trim_round(W: DeviceCsr, X, Y, G=None, lr=0.0, trim=1, dev_sq=None, dev_max=None, mean=None,
+               workspace: Workspace = None, tiled=None):
+    """One trimmed-mean consensus round on the current stream (dl_trim_round): per column every
+    agent drops the ``trim`` largest and the ``trim`` smallest of its neighbours' values of
+    X - lr G (X without G) and averages what is left with its own [+ deviation of Y].  Only W's
+    sparsity pattern is used -- the weights are ignored; every row needs exactly one diagonal
+    entry, at most 16 neighbours and, with trim >= 1, at least 2 trim + 1 (ValueError naming the
+    first offending row).  Y may be X itself.  ``tiled=(n_params, tile_cols)``: X, G, Y in the
+    column-tiled layout.  Returns False, launching nothing, when the round does not plan the LDS
+    tile kernel (path 1); there is no composed form."""
+    P = tiled[0] if tiled is not None else X.shape[1]
+    args = _trim_round_args(W, X, Y, G, lr, trim, dev_sq, dev_max, mean, tiled)
+    return _fused_round_run("dl_trim_round", args, W, P, workspace)
 
 
 class AdamState:
@@ -1136,6 +1194,28 @@ class GossipEngine:
         self._S.sub_(Gold)
         mix_round(self.W, self._S, self.D, workspace=self.ws, tiled=tiled)
         self.round(G=self.D, lr=lr, deviation=deviation, mean=mean)
+
+    def round_trim(self, G=None, lr=0.0, trim=1, deviation=False, mean=None):
+        """One trimmed-mean (BRIDGE-T / ByRDiE) round, X / Y ping-ponging as in ``round``: with
+        s = X - lr G (X without G; G in the resident layout), every agent a and column p takes its
+        n_a neighbours' s_j[p] in ascending order u_1 <= ... <= u_{n_a}, drops the ``trim`` = b
+        smallest and the b largest, and sets
+            x_a[p] <- fl((((0 + u_{b+1}) + ...) + u_{n_a-b} + s_a[p]) / float32(n_a - 2b + 1))
+        in fp32, every operation rounded on its own.  One agent's garbage therefore moves no
+        honest agent outside the range of its honest neighbourhood while each agent has at most b
+        bad neighbours.  W's WEIGHTS ARE IGNORED: a row's entries only name the closed
+        neighbourhood (exactly one diagonal entry, at most 16 neighbours, at least 2b + 1 with b
+        >= 1; ValueError otherwise).  NaN inputs give unspecified results.  There is no composed
+        fallback -- the N x deg x P gather does not fit memory at this engine's scale: where the
+        round does not plan the LDS tile kernel this raises RuntimeError with the planner's
+        text."""
+        if not trim_round(self.W, self.X, self.Y, G, lr, trim,
+                          dev_sq=self.dev_sq if deviation else None,
+                          dev_max=self.dev_max if deviation else None, mean=mean,
+                          workspace=self.ws,
+                          tiled=(self.P, self.T) if self.layout == "tiled" else None):
+            raise RuntimeError(_lib.load().dl_last_error().decode())
+        self.X, self.Y = self.Y, self.X
 
     def reset_adam(self, lr=None, betas=None):
         """Zero Adam's moments ``M`` and ``V`` and its step count (the state ``round_adam`` starts

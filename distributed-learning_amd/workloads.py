@@ -523,11 +523,16 @@ class MLPConsensusSGD:
     step count).  The step count lives on the device and every step ticks it, inside a captured
     graph too, so ``capture()`` needs no eager step first.  Needs emit="grad"; exclusive with
     ``tracking`` and with momentum / dampening / nesterov.  The default "sgd" is everything
-    above."""
+    above.
+    trim >= 1: the screened round instead of the plain one (``GossipEngine.round_trim``: per
+    coordinate every agent drops the ``trim`` largest and smallest of its neighbours' stepped
+    values and averages the rest with its own; W's weights are ignored), eager and under
+    capture / replay.  Needs emit="grad"; exclusive with ``tracking``, optimizer="adam", momentum
+    and weight decay."""
 
     def __init__(self, ann, eng, data, labels, lr, deviation=True, emit="auto", sampler=None,
                  momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False, tracking=False,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8):
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, trim=0):
         if eng.layout == "tiled" and ann.path != "fused":
             raise ValueError("the layered gradients read X row-major: use GossipEngine("
                              "layout='rows') or the fused kernel")
@@ -573,6 +578,13 @@ class MLPConsensusSGD:
         self.tracking = bool(tracking)
         if self.tracking and (momentum != 0.0 or weight_decay != 0.0 or emit != "grad"):
             raise ValueError("tracking needs emit='grad' and no momentum / weight_decay")
+        self.trim = int(trim)
+        if self.trim < 0:
+            raise ValueError(f"trim must be >= 0 (got {trim})")
+        if self.trim and (self.tracking or self.adam or momentum != 0.0 or weight_decay != 0.0 or
+                          emit != "grad"):
+            raise ValueError("trim needs emit='grad' and is exclusive with tracking, "
+                             "optimizer='adam', momentum and weight_decay")
         self.opt = dict(momentum=float(momentum), dampening=float(dampening),
                         weight_decay=float(weight_decay), nesterov=bool(nesterov))
         self.optimizer = not self.adam and (momentum != 0.0 or weight_decay != 0.0)
@@ -673,6 +685,8 @@ class MLPConsensusSGD:
         elif self.optimizer:
             self.eng.round_sgd(self.G, self.M, self.lr, first=self.steps_done == 0,
                                deviation=self.deviation, **self.opt)
+        elif self.trim:
+            self.eng.round_trim(self.G, self.lr, trim=self.trim, deviation=self.deviation)
         elif self.emit == "step":
             self.eng.round(src=self.G, deviation=self.deviation)
         else:

@@ -695,6 +695,59 @@ typedef struct dl_adam_round_args {
 int dl_adam_round_plan(const dl_adam_round_args *args, dl_mix_plan *plan);
 int dl_adam_round(const dl_adam_round_args *args, void *workspace, size_t ws_bytes,
                   dl_stream_t stream);
+/* One trimmed-mean consensus round in one HBM pass (no reference counterpart: every other round
+ * here is linear in the neighbours' values, so one agent that sends garbage moves each neighbour
+ * by w x garbage).  The screened round of BRIDGE-T / ByRDiE: per column every agent drops the
+ * `trim` largest and the `trim` smallest of its neighbours' values and averages what is left with
+ * its own.  Row a of W lists the closed neighbourhood: exactly one entry has col == a (the agent
+ * itself), the other n_a entries are the neighbours, a repeated neighbour counting once per entry.
+ * Only the sparsity pattern is used: THE WEIGHTS ARE IGNORED.  With b = trim, 0 <= b <= 7, and
+ * n_a <= 16, for every column p:
+ *   s_j    = x_j                         (g == NULL)
+ *   s_j    = fl(x_j - fl(lr g_j))        (g given: dl_mix_round's own step, same rounding)
+ *   u_1 <= ... <= u_{n_a}  = the neighbours' s_j[p] in ascending order
+ *   acc    = +0.0
+ *   acc    = fl(acc + u_i)   for i = b+1 ... n_a-b, in that order
+ *   acc    = fl(acc + s_a[p])
+ *   y_a[p] = fl(acc / (float)(n_a - 2b + 1))       IEEE division
+ * every operation rounded separately.  The fold starts at +0.0, so the order among values that
+ * compare equal (-0.0 against +0.0 included) cannot change a bit.  +-Inf sort as numbers.  The
+ * result for NaN inputs is unspecified.  With b >= 1 every row needs n_a >= 2b + 1; with b = 0 any
+ * n_a >= 0 is accepted (the plain unweighted neighbourhood average).
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   max_row_nnz / min_row_nnz are the caller's promises about W's row lengths (self included);
+ *     the library cannot read W.  A broken promise gives wrong values, never an out-of-range
+ *     access: a row is read for at most max_row_nnz entries.
+ *   y may be x itself with ldy == ldx (a workgroup stages all rows of its columns before it
+ *     writes them); layouts, strides and alignment as dl_mix_round's.
+ *   dev_sq / dev_max / mean describe y as dl_mix_round's do; workspace dl_mix_workspace_bytes.
+ *     They are always taken from y in two passes over the staged tile (a trimmed mean does not
+ *     preserve the column mean): W.doubly_stochastic is ignored.
+ *   DL_ERR_INVALID: args NULL; x or y NULL ("null x/y"); trim outside 0..7 ("trim must be in
+ *     0..7"); max_row_nnz outside 2..17 ("max_row_nnz must be in 2..17") or below min_row_nnz
+ *     ("below min_row_nnz"); min_row_nnz below 2 trim + 2 (trim >= 1) or 1 ("needs min_row_nnz");
+ *     W.uniform_row_nnz > 0 outside the promises ("contradicts the promised row lengths"); y
+ *     overlapping x other than being it and every other argument dl_mix_round itself refuses (the
+ *     texts say dl_mix_round); dl_trim_round_plan with plan NULL.
+ *   DL_ERR_UNSUPPORTED: any halo, partition or lagged-deviation field (halo, n_halo, mean_prev,
+ *     colsum_out, n_local_src, n_halo_blocks, partial_rows_out); rounds that plan path 2, 4 or 5
+ *     (LDS tile kernel only; there is no composed form).
+ *   DL_ERR_WORKSPACE: as dl_mix_round (deviation outputs without a 16-byte aligned workspace of
+ *     dl_mix_workspace_bytes).
+ *   Stream-ordered, no host synchronisation, no allocation: capturable in a hipGraph.
+ * dl_trim_round_plan: DL_OK and the configuration the round would run (dl_mix_round's for the same
+ * dl_mix_args), or the refusal, without touching the device. */
+typedef struct dl_trim_round_args {
+    dl_mix_args mix;      /* x, y, W (pattern only), g (nullable), lr, n_params, ld*, tile_cols,
+                             dev_sq, dev_max, mean; halo, n_halo, mean_prev, colsum_out,
+                             n_local_src, n_halo_blocks, partial_rows_out must be NULL / 0 */
+    int32_t trim;         /* b */
+    int32_t max_row_nnz;  /* promise: no row has more entries (self included); 2..17 */
+    int32_t min_row_nnz;  /* promise: no row has fewer; with trim >= 1 it must be >= 2*trim + 2 */
+} dl_trim_round_args;
+int dl_trim_round_plan(const dl_trim_round_args *args, dl_mix_plan *plan);
+int dl_trim_round(const dl_trim_round_args *args, void *workspace, size_t ws_bytes,
+                  dl_stream_t stream);
 /* out[r, j] = fl(fl(a s[r, j]) + fl(b z[r, j])) over n_rows x n_params (row strides lds_, ldz, ldo
  * >= n_params): dl_cheb_round's second line, so dl_mix_round into s and this call give the fused
  * round's bits -- the two-launch form, and the fallback where the round does not plan path 1.  out
