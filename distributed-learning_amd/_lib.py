@@ -128,6 +128,16 @@ class DlTrimRoundArgs(ctypes.Structure):
     _fields_ = [("mix", DlMixArgs), ("trim", _i32), ("max_row_nnz", _i32), ("min_row_nnz", _i32)]
 
 
+class DlEdgeSqdistArgs(ctypes.Structure):
+    _fields_ = [("mix", DlMixArgs), ("edge_sq", _vp), ("max_row_nnz", _i32),
+                ("min_row_nnz", _i32)]
+
+
+class DlClipWeightsArgs(ctypes.Structure):
+    _fields_ = [("W", DlCsr), ("edge_sq", _vp), ("tau", _vp), ("drop", _i32),
+                ("max_row_nnz", _i32), ("w_out", _vp), ("tau_out", _vp)]
+
+
 # the device state of dl_adam_tick (include/dlamd.h DL_ADAM_*): indices into a float64[8] tensor
 ADAM_T, ADAM_B1T, ADAM_B2T, ADAM_LR, ADAM_BETA1, ADAM_BETA2, ADAM_COEF = range(7)
 ADAM_STATE_LEN = 8
@@ -238,6 +248,10 @@ SIGNATURES = {
     "dl_adam_round": (_i32, [ctypes.POINTER(DlAdamRoundArgs), _vp, _sz, _vp]),
     "dl_trim_round_plan": (_i32, [ctypes.POINTER(DlTrimRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_trim_round": (_i32, [ctypes.POINTER(DlTrimRoundArgs), _vp, _sz, _vp]),
+    "dl_edge_sqdist_plan": (_i32, [ctypes.POINTER(DlEdgeSqdistArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_edge_sqdist_workspace_bytes": (_sz, [_i32, _i32, _i64]),
+    "dl_edge_sqdist": (_i32, [ctypes.POINTER(DlEdgeSqdistArgs), _vp, _sz, _vp]),
+    "dl_clip_weights": (_i32, [ctypes.POINTER(DlClipWeightsArgs), _vp]),
     "dl_axpby": (_i32, [_vp, _i64, _vp, _i64, _f32, _f32, _vp, _i64, _i32, _i64, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),

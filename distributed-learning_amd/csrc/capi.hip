@@ -2,7 +2,7 @@
 // the environment knobs, read once per call.  What an entry point checks and launches is decided
 // by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here their
 // description of a call is turned into launch_* calls and the step after them.  Shaped there:
-// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round, dl_adam_round, dl_trim_round), the one-pass
+// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist), the one-pass
 // deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch, dl_lenet_grad
 // and dl_lenet_eval.  The others (dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
 // deviation, the conversions, the step-rows functions, ...) check their own arguments here:
@@ -122,7 +122,8 @@ int zero_deviation(int32_t n_rows, float *dev_sq, float *dev_max, hipStream_t s)
 }
 
 // Issues the launches a shaping function of launch.h described and the zeroing or reduce after
-// them (kAfterPartialRows and kAfterTwoPass are dl_mix_round's own).  tile: what a tile launch
+// them (kAfterPartialRows and kAfterTwoPass are dl_mix_round's own, kAfterEdgeReduce
+// dl_edge_sqdist's).  tile: what a tile launch
 // is called in a HIP failure's text.
 int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, const char *tile,
         hipStream_t s) {
@@ -149,6 +150,9 @@ int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, cons
                 break;
             case dl::kLaunchTrimTile:
                 e = dl::launch_mix_trim_tile(l.t, l.r, l.chunks, l.dev, l.grid, l.lds, l.fast, s);
+                break;
+            case dl::kLaunchEdgeTile:
+                e = dl::launch_mix_edge_tile(l.t, l.e, l.chunks, l.grid, l.lds, l.fast, s);
                 break;
             case dl::kLaunchTileReg:
                 e = dl::launch_mix_tile_reg(l.t, l.chunks, l.head, l.tail_fmt, l.sgd, l.dev, l.grid,
@@ -745,6 +749,51 @@ int dl_trim_round(const dl_trim_round_args *args, void *workspace, size_t ws_byt
                   dl_stream_t stream) {
     return fused_round(dl::shape_trim_round, "mix_trim_tile_kernel", args, workspace, ws_bytes,
                        stream);
+}
+
+int dl_edge_sqdist_plan(const dl_edge_sqdist_args *args, dl_mix_plan *plan) {
+    return fused_round_plan(dl::shape_edge_sqdist, args, plan);
+}
+
+size_t dl_edge_sqdist_workspace_bytes(int32_t n_rows, int32_t max_row_nnz, int64_t n_params) {
+    (void)n_params;
+    return dl::edge_workspace_bytes(n_rows, max_row_nnz, device_cus(), dl::read_knobs());
+}
+
+int dl_edge_sqdist(const dl_edge_sqdist_args *args, void *workspace, size_t ws_bytes,
+                   dl_stream_t stream) {
+    g_err.clear();
+    dl::Launches L;
+    char err[dl::kErrLen];
+    int rc = dl::shape_edge_sqdist(args, device_cus(), dl::read_knobs(), workspace, ws_bytes,
+                                   nullptr, &L, err);
+    if (rc) return status(rc, err);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = run(L, nullptr, nullptr, nullptr, "mix_edge_tile_kernel", s);
+    if (rc) return rc;
+    const hipError_t e = dl::launch_edge_reduce(L.l[0].t, L.l[0].e, L.partial, L.parts,
+                                                args->edge_sq, s);
+    return e == hipSuccess ? DL_OK : hip_fail(e, "edge_reduce launch");
+}
+
+int dl_clip_weights(const dl_clip_weights_args *a, dl_stream_t stream) {
+    g_err.clear();
+    if (!a) return fail(DL_ERR_INVALID, "dl_clip_weights: args is NULL");
+    const dl_csr &W = a->W;
+    if (W.n_rows <= 0 || W.nnz < 0)
+        return fail(DL_ERR_INVALID, "dl_clip_weights: n_rows must be > 0, nnz >= 0");
+    if (!W.row_ptr || !W.col || !W.w || !a->edge_sq || !a->w_out)
+        return fail(DL_ERR_INVALID, "dl_clip_weights: null row_ptr/col/w/edge_sq/w_out");
+    if (!a->tau && (a->drop < 1 || a->drop > 16))
+        return fail(DL_ERR_INVALID, "dl_clip_weights: without tau, drop must be in 1..16 (got %d)",
+                    a->drop);
+    if (a->max_row_nnz < 2 || a->max_row_nnz > 17)
+        return fail(DL_ERR_INVALID, "dl_clip_weights: max_row_nnz must be in 2..17 (got %d)",
+                    a->max_row_nnz);
+    const hipError_t e = dl::launch_clip_weights(W.n_rows, W.nnz, a->max_row_nnz, W.row_ptr, W.col,
+                                                 W.w, a->edge_sq, a->tau, a->drop, a->w_out,
+                                                 a->tau_out, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DL_OK : hip_fail(e, "clip_weights_kernel launch");
 }
 
 int dl_adam_step(const dl_adam_args *a, dl_stream_t stream) {

@@ -62,6 +62,20 @@ hipError_t launch_mix_adam_tile(const TileArgs &a, const AdamTileArgs &q, int ch
 // weights are not read), plus the trim and the row-length promises (launch.h TrimTileArgs).
 hipError_t launch_mix_trim_tile(const TileArgs &a, const TrimTileArgs &q, int chunks, bool dev,
                                 int grid, int lds_bytes, bool fast, hipStream_t s);
+// The per-edge distance pass (mix_edge.hip) for one launch shaped by shape_edge_sqdist: TileArgs
+// as for launch_mix_trim_tile (y is not written), plus this launch's partial rows and the
+// row-length promises (launch.h EdgeTileArgs) ...
+hipError_t launch_mix_edge_tile(const TileArgs &a, const EdgeTileArgs &q, int chunks, int grid,
+                                int lds_bytes, bool fast, hipStream_t s);
+// ... the reduce after the launches: edge_sq[e] = the `parts` partial rows' sum in order, slot ->
+// CSR entry, +0.0 on the diagonal ...
+hipError_t launch_edge_reduce(const TileArgs &a, const EdgeTileArgs &q, const float *partial,
+                              int parts, float *edge_sq, hipStream_t s);
+// ... and dl_clip_weights' kernel: one thread per row
+hipError_t launch_clip_weights(int n_rows, int nnz, int max_row_nnz, const int32_t *rowptr,
+                               const int32_t *col, const float *w, const float *edge_sq,
+                               const float *tau, int drop, float *w_out, float *tau_out,
+                               hipStream_t s);
 // out = fl(fl(a * s) + fl(b * z)) over n_rows x n_params (aux_kernels.hip); vec: float4 accesses
 hipError_t launch_axpby(const float *src, int64_t lds_, const float *z, int64_t ldz, float a,
                         float b, float *out, int64_t ldo, int n_rows, int64_t n_params, bool vec,

@@ -703,6 +703,84 @@ int shape_trim_round(const dl_trim_round_args *a, int n_cus, const Knobs &k, voi
     return DL_OK;
 }
 
+size_t edge_workspace_bytes(int32_t n_rows, int32_t max_row_nnz, int n_cus, const Knobs &k) {
+    if (n_rows <= 0 || max_row_nnz < 2) return 0;
+    const int nw = edge_slots(max_row_nnz - 1);
+    return partial_bytes(max_parts(n_cus, k), (int64_t)n_rows * nw) + kWsAlign;
+}
+
+int shape_edge_sqdist(const dl_edge_sqdist_args *a, int n_cus, const Knobs &k, void *ws,
+                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_edge_sqdist: args is NULL");
+    if (!a->mix.x || !a->edge_sq) return fail(err, DL_ERR_INVALID, "dl_edge_sqdist: null x/edge_sq");
+    if (a->mix.y || a->mix.dev_sq || a->mix.dev_max || a->mix.mean)
+        return fail(err, DL_ERR_INVALID, "dl_edge_sqdist: y, dev_sq, dev_max and mean must be NULL "
+                                         "(x and g are only read)");
+    if (a->max_row_nnz < 2 || a->max_row_nnz > 17)
+        return fail(err, DL_ERR_INVALID, "dl_edge_sqdist: max_row_nnz must be in 2..17 (self and "
+                                         "at most 16 neighbours; got %d)", a->max_row_nnz);
+    if (a->max_row_nnz < a->min_row_nnz)
+        return fail(err, DL_ERR_INVALID, "dl_edge_sqdist: max_row_nnz %d below min_row_nnz %d",
+                    a->max_row_nnz, a->min_row_nnz);
+    if (a->min_row_nnz < 1)
+        return fail(err, DL_ERR_INVALID, "dl_edge_sqdist: min_row_nnz must be >= 1 (the self "
+                                         "entry; got %d)", a->min_row_nnz);
+    const int32_t uni = a->mix.W.uniform_row_nnz;
+    if (uni > 0 && (uni > a->max_row_nnz || uni < a->min_row_nnz))
+        return fail(err, DL_ERR_INVALID, "dl_edge_sqdist: uniform_row_nnz %d contradicts the "
+                                         "promised row lengths %d..%d", uni, a->min_row_nnz,
+                    a->max_row_nnz);
+    // the round's checks, plan and launches for y = x in place: the pass stages what that round
+    // stages and writes no y
+    dl_mix_args m = a->mix;
+    m.y = const_cast<float *>(m.x);
+    m.ldy = m.ldx;
+    const FusedRound r{"dl_edge_sqdist", "distance", kLaunchEdgeTile, nullptr, 0};
+    int rc = whole_round(r, m, err);
+    if (rc) return rc;
+    const Layout lay(m);
+    const size_t eb = (size_t)m.W.nnz * 4;
+    if (eb && (overlaps(a->edge_sq, eb, m.x, lay.span(m.ldx)) ||
+               (m.g && overlaps(a->edge_sq, eb, m.g, lay.span(m.ldg)))))
+        return fail(err, DL_ERR_INVALID, "dl_edge_sqdist: edge_sq overlaps x or g");
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_edge_sqdist_plan: plan is NULL");
+    dl_mix_plan pub;
+    rc = plan_and_shape(r, m, n_cus, k, nullptr, 0, &pub, out, err);
+    if (rc) return rc;
+    const int chunks = pub.tile_cols / 4, max_nbrs = a->max_row_nnz - 1;
+    if (!edge_slots_fit(chunks, m.W.n_rows, max_nbrs))
+        return fail(err, DL_ERR_UNSUPPORTED,
+                    "dl_edge_sqdist: %d rows per thread x %d neighbour slots exceed the pass's %d "
+                    "accumulator registers (%d agents at tile_cols %d); a smaller tile_cols lowers "
+                    "the rows per thread", tile_passes(chunks, m.W.n_rows, true),
+                    edge_slots(max_nbrs), kEdgeAccumulators, m.W.n_rows, pub.tile_cols);
+    if (plan) *plan = pub;
+    if (!out) return DL_OK;
+    int parts = 0;
+    for (int i = 0; i < out->n; ++i) parts += out->l[i].grid;
+    const int64_t prow = (int64_t)m.W.n_rows * edge_slots(max_nbrs);
+    const size_t need = partial_bytes(parts, prow);
+    if (!ws_holds(ws, ws_bytes, need))
+        return fail(err, DL_ERR_WORKSPACE, "dl_edge_sqdist: needs a 16-byte aligned workspace of "
+                                           "%zu bytes (got %zu; dl_edge_sqdist_workspace_bytes)",
+                    need, ws ? ws_bytes : (size_t)0);
+    float *partial = static_cast<float *>(ws);
+    int first = 0;
+    for (int i = 0; i < out->n; ++i) {
+        Launch &l = out->l[i];
+        l.t.y = nullptr;
+        l.e.partial = partial + (size_t)first * prow;
+        l.e.max_nbrs = max_nbrs;
+        l.e.uniform_nbrs = uni > 0 ? uni - 1 : 0;
+        first += l.grid;
+    }
+    out->after = kAfterEdgeReduce;
+    out->partial = partial;
+    out->parts = parts;
+    out->rows = m.W.n_rows;
+    return DL_OK;
+}
+
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err) {
     reset(out);

@@ -3,7 +3,7 @@
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
 // rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round,
-// dl_track_round, dl_adam_round, dl_trim_round and their plan queries),
+// dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist and their plan queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -183,6 +183,22 @@ struct TrimTileArgs {
     int32_t uniform_nbrs;
 };
 
+// The per-edge distance pass (mix_edge.hip): this launch's partial rows [grid][n_rows][NW] in the
+// workspace, the promised longest row's neighbours (picks NW = edge_slots) and, for a regular
+// graph, every row's neighbour count (0: read per row).
+struct EdgeTileArgs {
+    float *partial;
+    int32_t max_nbrs;
+    int32_t uniform_nbrs;
+};
+// Slots per row, and whether the pass holds them: rows per thread x slots <= 64 accumulator
+// registers (the FAST and the guarded kernels both run tile_passes(chunks, n_rows, true) rows)
+constexpr int kEdgeAccumulators = 64;
+constexpr int edge_slots(int max_nbrs) { return max_nbrs <= 4 ? 4 : max_nbrs <= 8 ? 8 : 16; }
+constexpr bool edge_slots_fit(int chunks, int n_rows, int max_nbrs) {
+    return tile_passes(chunks, n_rows, true) * edge_slots(max_nbrs) <= kEdgeAccumulators;
+}
+
 // One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
 // launch_* functions of dl_internal.h take them.
 enum LaunchKind : int32_t {
@@ -197,6 +213,7 @@ enum LaunchKind : int32_t {
     kLaunchTrackTile, // launch_mix_track_tile(t, k, chunks, dev, grid, lds, fast)
     kLaunchAdamTile,  // launch_mix_adam_tile(t, a, chunks, dev, grid, lds, fast)
     kLaunchTrimTile,  // launch_mix_trim_tile(t, r, chunks, dev, grid, lds, fast)
+    kLaunchEdgeTile,  // launch_mix_edge_tile(t, e, chunks, grid, lds, fast)
 };
 struct Launch {
     int32_t kind;
@@ -211,6 +228,7 @@ struct Launch {
     TrackTileArgs k;           // kLaunchTrackTile
     AdamTileArgs a;            // kLaunchAdamTile
     TrimTileArgs r;            // kLaunchTrimTile
+    EdgeTileArgs e;            // kLaunchEdgeTile
 };
 // What follows the launches on the stream.
 enum After : int32_t {
@@ -219,13 +237,14 @@ enum After : int32_t {
     kAfterReduce,       // launch_dev_reduce(partial, parts, rows, dev_sq, dev_max, max_zeroed)
     kAfterPartialRows,  // leave the partial rows in the workspace, *partial_rows_out = parts
     kAfterTwoPass,      // the two-pass deviation of y (the gather path)
+    kAfterEdgeReduce,   // launch_edge_reduce(l[0].t, l[0].e, partial, parts, edge_sq)
 };
 struct Launches {
     int32_t n;
     Launch l[2];
     int32_t after;
-    const float *partial;   // kAfterReduce
-    int32_t parts, rows;    // kAfterReduce, kAfterPartialRows (parts)
+    const float *partial;   // kAfterReduce, kAfterEdgeReduce
+    int32_t parts, rows;    // kAfterReduce, kAfterPartialRows (parts), kAfterEdgeReduce (parts)
     bool max_zeroed;
 };
 
@@ -270,6 +289,14 @@ int shape_adam_round(const dl_adam_round_args *a, int n_cus, const Knobs &k, voi
 // other and uniform_row_nnz; mean_from_inputs cleared; kLaunchTrimTile with TrimTileArgs
 int shape_trim_round(const dl_trim_round_args *a, int n_cus, const Knobs &k, void *ws,
                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
+// the distance pass: no y and no deviation output (x and g are only read), edge_sq apart from x
+// and g, the row-length promises; the plan is dl_mix_round's for the same x and g, refused unless
+// path 1 and unless edge_slots_fit; the workspace holds every workgroup's partial row
+// (edge_workspace_bytes); kLaunchEdgeTile with EdgeTileArgs, then kAfterEdgeReduce
+int shape_edge_sqdist(const dl_edge_sqdist_args *a, int n_cus, const Knobs &k, void *ws,
+                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
+// ... its workspace for any plan: max_parts partial rows of n_rows x edge_slots floats
+size_t edge_workspace_bytes(int32_t n_rows, int32_t max_row_nnz, int n_cus, const Knobs &k);
 int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                  size_t ws_bytes, Launches *out, char *err);
 int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,

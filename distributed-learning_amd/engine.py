@@ -6,6 +6,7 @@ This replaces, per round, the reference's Python loop of ``Mixer._mix_params_onc
 fresh fp32 array per agent and term.  Flattening models to X happens once per ``mix()`` call
 (mixer.py:26), not per round.
 """
+import copy
 import ctypes
 import math
 import os
@@ -477,6 +478,91 @@ def trim_round(W: DeviceCsr, X, Y, G=None, lr=0.0, trim=1, dev_sq=None, dev_max=
     P = tiled[0] if tiled is not None else X.shape[1]
     args = _trim_round_args(W, X, Y, G, lr, trim, dev_sq, dev_max, mean, tiled)
     return _fused_round_run("dl_trim_round", args, W, P, workspace)
+
+
+def _edge_sqdist_args(W, X, G, lr, out, tiled):
+    # (the operands' checks of a round writing X in place; the pass itself writes no y)
+    mix, _ = _fused_round_operands("edge_sqdist", None, W, X, X, G, lr, None, None, None, tiled,
+                                   ())
+    mix.y, mix.ldy = None, 0
+    hi, lo = W.trim_promises()
+    if hi > 17:
+        bad = int(np.argmax(np.diff(np.asarray(W.csr.rowptr, np.int64)) > 17))
+        raise ValueError(f"edge_sqdist takes at most 16 neighbours a row: row {bad} has more")
+    if out is not None and (out.dtype != torch.float32 or out.device != W.device or
+                            out.shape != (W.nnz,) or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 [{W.nnz}] tensor on {W.device}")
+    return _lib.DlEdgeSqdistArgs(mix, _lib.ptr(out), max(hi, 2), lo), max(hi, 2)
+
+
+def edge_sqdist_plan(W: DeviceCsr, X, G=None, tiled=None):
+    """dl_edge_sqdist_plan: the configuration ``edge_sqdist`` would run for these operands, or
+    None when the pass does not take them (a plan path other than 1, or more accumulators than
+    its registers hold)."""
+    dummy = torch.empty(1, dtype=torch.float32, device=W.device)
+    args, _ = _edge_sqdist_args(W, X, G, 0.0, None, tiled)
+    args.edge_sq = _lib.ptr(dummy)
+    return _fused_round_plan("dl_edge_sqdist_plan", lambda dev_sq, dev_max: args, W, False)
+
+
+def edge_sqdist(W: DeviceCsr, X, G=None, lr=0.0, out=None, workspace: Workspace = None,
+                tiled=None):
+    """Per-edge squared distances on the current stream (dl_edge_sqdist): for every CSR entry e
+    of row a with column j, E[e] = sum_p (s_j[p] - s_a[p])^2 over all columns with s = X - lr G
+    (X without G), by direct differences in fp32; +0.0 on the diagonal entries.  X and G are only
+    read, once.  Only W's sparsity pattern is used: exactly one diagonal entry and at most 16
+    neighbours in every row (ValueError naming the first offending row).  ``tiled=(n_params,
+    tile_cols)``: X, G in the column-tiled layout.  Returns E (``out``, or a new [nnz] tensor) --
+    or False, launching nothing, when the pass does not plan the LDS tile kernel (path 1) or its
+    accumulators do not fit; there is no composed form."""
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(W.nnz, dtype=torch.float32, device=W.device)
+    args, hi = _edge_sqdist_args(W, X, G, lr, out, tiled)
+    P = tiled[0] if tiled is not None else X.shape[1]
+    workspace = workspace or Workspace(W.device)
+    wp, wn = workspace.ptr_size(lib.dl_edge_sqdist_workspace_bytes(W.n_rows, hi, P))
+    rc = lib.dl_edge_sqdist(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc, "dl_edge_sqdist")
+    return out
+
+
+def _clip_drop(W, tau, drop):
+    """clip_weights' ``drop`` checked against the host CSR (before anything is launched)."""
+    drop = int(drop)
+    if tau is None:
+        if drop < 1:
+            raise ValueError("clip_weights needs tau or drop >= 1")
+        if W.trim_promises()[1] < drop + 2:
+            nnz = np.diff(np.asarray(W.csr.rowptr, np.int64))
+            bad = int(np.flatnonzero(nnz < drop + 2)[0])
+            raise ValueError(f"clip_weights with drop {drop} needs {drop + 1} neighbours in every "
+                             f"row: row {bad} has {int(nnz[bad]) - 1}")
+    return drop
+
+
+def clip_weights(W: DeviceCsr, E, out_w, tau=None, drop=0, tau_out=None):
+    """The clipped row of W on the current stream (dl_clip_weights): with d_e = sqrt(E[e]) and
+    c_e = min(1, tau_a / d_e) (1 at d_e = 0), out_w[e] = w_e c_e off the diagonal, and the weight
+    clipped off the row's edges added to its diagonal entry, so ``mix_round`` with these weights
+    is the clipped-gossip update.  ``tau``: a float32 [n_rows] device tensor; None: the kernel
+    takes tau_a = the (drop + 1)-th largest distance among row a's neighbours, drop >= 1 -- every
+    row then needs drop + 1 neighbours (ValueError naming the first offending row).  ``tau_out``
+    (optional, [n_rows]) receives the radius used."""
+    lib = _lib.load()
+    hi, _ = W.trim_promises()
+    drop = _clip_drop(W, tau, drop)
+    for name, t, k in (("E", E, W.nnz), ("out_w", out_w, W.nnz), ("tau", tau, W.n_rows),
+                       ("tau_out", tau_out, W.n_rows)):
+        if t is not None and (t.dtype != torch.float32 or t.device != W.device or
+                              t.shape != (k,) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 [{k}] tensor on {W.device}")
+    args = _lib.DlClipWeightsArgs(W.c_struct(), _lib.ptr(E), _lib.ptr(tau), drop, max(hi, 2),
+                                  _lib.ptr(out_w), _lib.ptr(tau_out))
+    _lib.check(lib.dl_clip_weights(ctypes.byref(args), _lib.stream_handle(W.device)),
+               "dl_clip_weights")
 
 
 class AdamState:
@@ -1050,6 +1136,7 @@ class GossipEngine:
         self.dev_sq = torch.zeros(self.n, dtype=torch.float32, device=self.device)
         self.dev_max = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.ws = Workspace(self.device)
+        self.Wc = None      # round_clip's state (_clip_state): Wc, edge_sq, clip_tau
         self._slot = 0      # stagger slot of the next resident buffer (X, Y, G, ...)
         self.X = self.layout_like(X) if X is not None else self._empty()
         self.Y = self._empty()
@@ -1095,11 +1182,31 @@ class GossipEngine:
         out[self.order] = self.dev_sq
         return out
 
-    def reserve_workspace(self, deviation=True):
-        """Allocate the round's scratch now (so a hipGraph capture allocates nothing)."""
-        if deviation:
-            lib = _lib.load()
-            self.ws.get(lib.dl_mix_workspace_bytes(self.n, self.W.n_src - self.n, self.P))
+    def reserve_workspace(self, deviation=True, clip=False):
+        """Allocate the round's scratch now (so a hipGraph capture allocates nothing); clip:
+        ``round_clip``'s state and the distance pass's workspace too."""
+        lib = _lib.load()
+        need = lib.dl_mix_workspace_bytes(self.n, self.W.n_src - self.n, self.P) if deviation else 0
+        if clip:
+            self._clip_state()
+            need = max(need, lib.dl_edge_sqdist_workspace_bytes(
+                self.n, max(self.W.trim_promises()[0], 2), self.P))
+        if need:
+            self.ws.get(need)
+
+    def _clip_state(self):
+        """round_clip's buffers, on first use: the per-edge distances ``edge_sq`` [nnz], the radii
+        ``clip_tau`` [N], and ``Wc`` -- W's pattern (the same rowptr / col tensors) with weights
+        of its own, promised neither doubly stochastic nor shared between rows: clipping breaks
+        both."""
+        if self.Wc is None:
+            self.W.trim_promises()
+            self.edge_sq = torch.zeros(self.W.nnz, dtype=torch.float32, device=self.device)
+            self.clip_tau = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+            Wc = copy.copy(self.W)
+            Wc.w = self.W.w.clone()
+            Wc.doubly_stochastic = Wc.shared_row_weights = 0
+            self.Wc = Wc
 
     def round(self, G=None, lr=0.0, deviation=False, mean=None, halo=None, src=None):
         """G must already be in the resident layout (``layout_like``).  src (optional, resident
@@ -1215,6 +1322,40 @@ class GossipEngine:
                           workspace=self.ws,
                           tiled=(self.P, self.T) if self.layout == "tiled" else None):
             raise RuntimeError(_lib.load().dl_last_error().decode())
+        self.X, self.Y = self.Y, self.X
+
+    def round_clip(self, G=None, lr=0.0, tau=None, drop=1, deviation=False, mean=None):
+        """One clipped-gossip round (self-centred clipping; He, Karimireddy, Jaggi), X / Y
+        ping-ponging as in ``round``: with s = X - lr G (X without G; G in the resident layout),
+            x_a <- s_a + sum_{j in N(a)} w_aj min(1, tau_a / ||s_j - s_a||_2) (s_j - s_a).
+        W's weights are kept -- where nobody misbehaves and tau is large the round is ``round``
+        bit for bit -- and an honest agent moves at most tau_a sum_j |w_aj| whatever a neighbour
+        sends (finite garbage; +-Inf or NaN rows are not supported).  Three launches on the
+        current stream, capture-safe: ``edge_sqdist`` into ``edge_sq``, ``clip_weights`` into
+        ``Wc.w`` (the clipped weight goes back to the diagonal), and ``mix_round`` with ``Wc``,
+        whose bits it therefore has.  ``tau``: a float or a float32 [N] device tensor (per slot
+        under an engine row order); it overrides ``drop``.  Without it tau_a is the distance of
+        agent a's (drop + 1)-th farthest neighbour: the ``drop`` farthest are pulled in to it
+        (every row needs drop + 1 neighbours, exactly one diagonal entry and at most 16
+        neighbours; ValueError otherwise).  ``clip_tau`` holds the radii used.  The distance pass
+        has no composed fallback: where it does not plan the LDS tile kernel this raises
+        RuntimeError with the planner's text; the final round may take any path."""
+        self._clip_state()
+        _clip_drop(self.W, tau, drop)      # a refused round launches nothing
+        tiled = (self.P, self.T) if self.layout == "tiled" else None
+        if edge_sqdist(self.W, self.X, G, lr, out=self.edge_sq, workspace=self.ws,
+                       tiled=tiled) is False:
+            raise RuntimeError(_lib.load().dl_last_error().decode())
+        tau_out = self.clip_tau
+        if tau is not None and not isinstance(tau, torch.Tensor):
+            tau, tau_out = self.clip_tau.fill_(float(tau)), None
+        elif tau is self.clip_tau:
+            tau_out = None
+        clip_weights(self.W, self.edge_sq, self.Wc.w, tau=tau, drop=drop, tau_out=tau_out)
+        mix_round(self.Wc, self.X, self.Y, G=G, lr=lr,
+                  dev_sq=self.dev_sq if deviation else None,
+                  dev_max=self.dev_max if deviation else None, mean=mean, workspace=self.ws,
+                  tiled=tiled)
         self.X, self.Y = self.Y, self.X
 
     def reset_adam(self, lr=None, betas=None):

@@ -528,11 +528,15 @@ class MLPConsensusSGD:
     coordinate every agent drops the ``trim`` largest and smallest of its neighbours' stepped
     values and averages the rest with its own; W's weights are ignored), eager and under
     capture / replay.  Needs emit="grad"; exclusive with ``tracking``, optimizer="adam", momentum
-    and weight decay."""
+    and weight decay.
+    clip >= 1: clipped gossip instead (``GossipEngine.round_clip(drop=clip)``: W's weights kept,
+    each agent's ``clip`` farthest neighbours pulled in to the distance of the next one), eager
+    and under capture / replay.  Needs emit="grad"; exclusive with ``trim``, ``tracking``,
+    optimizer="adam", momentum and weight decay."""
 
     def __init__(self, ann, eng, data, labels, lr, deviation=True, emit="auto", sampler=None,
                  momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False, tracking=False,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, trim=0):
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, trim=0, clip=0):
         if eng.layout == "tiled" and ann.path != "fused":
             raise ValueError("the layered gradients read X row-major: use GossipEngine("
                              "layout='rows') or the fused kernel")
@@ -584,6 +588,13 @@ class MLPConsensusSGD:
         if self.trim and (self.tracking or self.adam or momentum != 0.0 or weight_decay != 0.0 or
                           emit != "grad"):
             raise ValueError("trim needs emit='grad' and is exclusive with tracking, "
+                             "optimizer='adam', momentum and weight_decay")
+        self.clip = int(clip)
+        if self.clip < 0:
+            raise ValueError(f"clip must be >= 0 (got {clip})")
+        if self.clip and (self.trim or self.tracking or self.adam or momentum != 0.0 or
+                          weight_decay != 0.0 or emit != "grad"):
+            raise ValueError("clip needs emit='grad' and is exclusive with trim, tracking, "
                              "optimizer='adam', momentum and weight_decay")
         self.opt = dict(momentum=float(momentum), dampening=float(dampening),
                         weight_decay=float(weight_decay), nesterov=bool(nesterov))
@@ -687,6 +698,8 @@ class MLPConsensusSGD:
                                deviation=self.deviation, **self.opt)
         elif self.trim:
             self.eng.round_trim(self.G, self.lr, trim=self.trim, deviation=self.deviation)
+        elif self.clip:
+            self.eng.round_clip(self.G, self.lr, drop=self.clip, deviation=self.deviation)
         elif self.emit == "step":
             self.eng.round(src=self.G, deviation=self.deviation)
         else:
@@ -706,7 +719,7 @@ class MLPConsensusSGD:
         if self.optimizer and self.steps_done == 0:
             raise RuntimeError("run one eager step before capture(): the first step of "
                                "momentum SGD differs from the ones a graph replays")
-        self.eng.reserve_workspace(self.deviation)
+        self.eng.reserve_workspace(self.deviation, clip=bool(self.clip))
         done = self.steps_done
         # (recording a step advances the host mirror of Adam's step count, not the device's)
         adam_host = (self.eng.adam.t, self.eng.adam.b1t, self.eng.adam.b2t) if self.adam else None

@@ -748,6 +748,91 @@ typedef struct dl_trim_round_args {
 int dl_trim_round_plan(const dl_trim_round_args *args, dl_mix_plan *plan);
 int dl_trim_round(const dl_trim_round_args *args, void *workspace, size_t ws_bytes,
                   dl_stream_t stream);
+/* Per-edge squared distances in one HBM pass, and the clipped-gossip weights made from them (no
+ * reference counterpart).  Clipped gossip (self-centred clipping; He, Karimireddy, Jaggi) is the
+ * robust round that keeps W's weights: with s_a = x_a - lr g_a,
+ *   y_a = s_a + sum_{j in N(a)} w_aj min(1, tau_a / ||s_j - s_a||_2) (s_j - s_a),
+ * which is the plain round y = W' s for the row-rewritten W' of dl_clip_weights below; what the
+ * rounds lacked is ||s_j - s_a||^2 over all n_params columns, for every edge.
+ *
+ * dl_edge_sqdist: for every CSR entry e of row a of W with column j
+ *   s_j  = x_j                         (g == NULL)
+ *   s_j  = fl(x_j - fl(lr g_j))        (g given: dl_mix_round's own step, same rounding)
+ *   E[e] = sum_p fl(fl(s_j[p] - s_a[p])^2)
+ * by direct differences in fp32, every operation rounded separately; the order of the sum is the
+ * plan's (it is the same from run to run for one plan, and any order is within (n_params + 3)
+ * 2^-24 E of the exact sum of the same terms' squares).  edge_sq is [W.nnz] fp32 in CSR entry
+ * order; the diagonal entry of a row (the first with col == a) is written as +0.0.  x and g are
+ * only read; 8 B per element cross HBM with g and 4 B without, whatever the graph.  Only W's
+ * sparsity pattern is used.  Non-finite x or g give unspecified results (an overflowing difference
+ * gives E = +Inf, which dl_clip_weights turns into a weight of 0 -- and 0 x Inf is NaN in the
+ * round that follows: finite garbage of any size is the supported case).
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   max_row_nnz / min_row_nnz are the caller's promises about W's row lengths (self included), as
+ *     dl_trim_round's; every row has exactly one diagonal entry.  A broken promise gives wrong
+ *     values, never an out-of-range access: a row is read for at most max_row_nnz entries and the
+ *     entries of a longer row beyond them are written as +0.0.
+ *   The pass holds rows-per-thread x slots accumulators in registers, slots = 4, 8 or 16 >=
+ *     max_row_nnz - 1 and rows per thread = 2, 4 or 8 >= n_rows x tile_cols / 4096: their product
+ *     is at most 64.
+ *   workspace: dl_edge_sqdist_workspace_bytes(n_rows, max_row_nnz, n_params), 16-byte aligned
+ *     (every workgroup's partial sums, added in workgroup order by a second small kernel).
+ *   DL_ERR_INVALID: args NULL ("args is NULL"); x or edge_sq NULL ("null x/edge_sq"); y, dev_sq,
+ *     dev_max or mean set ("y, dev_sq, dev_max and mean must be NULL"); max_row_nnz outside 2..17
+ *     ("max_row_nnz must be in 2..17") or below min_row_nnz ("below min_row_nnz"); min_row_nnz < 1
+ *     ("min_row_nnz must be >= 1"); W.uniform_row_nnz > 0 outside the promises ("contradicts the
+ *     promised row lengths"); edge_sq overlapping x or g ("edge_sq overlaps"); every other
+ *     argument dl_mix_round itself refuses (the texts say dl_mix_round); dl_edge_sqdist_plan with
+ *     plan NULL.
+ *   DL_ERR_UNSUPPORTED: any halo, partition or lagged-deviation field; rounds that plan path 2, 4
+ *     or 5 (LDS tile kernel only; there is no composed form: the n_rows x degree x n_params gather
+ *     fits no memory at this scale); more than 64 accumulators ("accumulator registers": a smaller
+ *     tile_cols lowers the rows per thread).
+ *   DL_ERR_WORKSPACE: workspace NULL, not 16-byte aligned or short ("workspace").
+ *   Stream-ordered, no host synchronisation, no allocation: capturable in a hipGraph.
+ * dl_edge_sqdist_plan: DL_OK and the configuration the pass would run (dl_mix_round's for the
+ * same x and g), or the refusal, without touching the device. */
+typedef struct dl_edge_sqdist_args {
+    dl_mix_args mix;      /* x, W (pattern only), g (nullable), lr, n_params, ldx, ldg, tile_cols;
+                             y, dev_sq, dev_max, mean and every halo / partition field NULL / 0 */
+    float *edge_sq;       /* [W.nnz] */
+    int32_t max_row_nnz;  /* promise: no row has more entries (self included); 2..17 */
+    int32_t min_row_nnz;  /* promise: no row has fewer; >= 1 */
+} dl_edge_sqdist_args;
+int dl_edge_sqdist_plan(const dl_edge_sqdist_args *args, dl_mix_plan *plan);
+size_t dl_edge_sqdist_workspace_bytes(int32_t n_rows, int32_t max_row_nnz, int64_t n_params);
+int dl_edge_sqdist(const dl_edge_sqdist_args *args, void *workspace, size_t ws_bytes,
+                   dl_stream_t stream);
+/* dl_clip_weights: the clipped row of W on the device, one thread per row.  For row a with
+ * radius tau_a, visiting the row's entries e in CSR order:
+ *   d_e  = sqrt(E[e])                              correctly rounded
+ *   c_e  = d_e == 0 ? 1 : fminf(1, tau_a / d_e)    IEEE division
+ *   w'_e = fl(w_e c_e)                             for e off the diagonal
+ *   w'_aa: t = w_aa; for each off-diagonal e in CSR order: t = fl(t + fl(w_e - w'_e))
+ * so the weight clipped off an edge goes back to the agent's own entry: a row of W' sums to what
+ * the row of W summed to, up to rounding, with every c_e = 1 (tau = +Inf) W' is W bit for bit,
+ * and dl_mix_round with W' (doubly_stochastic = 0, shared_row_weights = 0: clipping breaks both)
+ * is the clipped-gossip update above with the round's usual bit-specified left fold.
+ *   tau: device float[n_rows], so a captured step can change it without a host round trip.  NULL:
+ *     the kernel chooses it, drop = b >= 1: tau_a = sqrt of the (b + 1)-th largest E among row a's
+ *     neighbour entries -- the b farthest neighbours are pulled in to the distance of the next
+ *     one; every row needs b + 1 neighbours (a shorter row gets tau_a = 0).  tau overrides drop.
+ *   tau_out: nullable float[n_rows], the radius used.  w_out: [W.nnz]; it may be W.w itself.
+ *   tau <= 0 and non-finite E give unspecified results.  Entries beyond max_row_nnz of a longer
+ *     row than promised keep their weight.
+ *   DL_ERR_INVALID: args NULL; W.row_ptr, W.col, W.w, edge_sq or w_out NULL ("null
+ *     row_ptr/col/w/edge_sq/w_out"); n_rows <= 0 or nnz < 0; tau NULL with drop outside 1..16
+ *     ("drop must be in 1..16"); max_row_nnz outside 2..17. */
+typedef struct dl_clip_weights_args {
+    dl_csr W;              /* row_ptr, col, w, n_rows, nnz */
+    const float *edge_sq;  /* [W.nnz], dl_edge_sqdist's */
+    const float *tau;      /* [n_rows], nullable with drop >= 1 */
+    int32_t drop;          /* b; read when tau is NULL */
+    int32_t max_row_nnz;   /* promise, as dl_edge_sqdist's */
+    float *w_out;          /* [W.nnz] */
+    float *tau_out;        /* [n_rows], nullable */
+} dl_clip_weights_args;
+int dl_clip_weights(const dl_clip_weights_args *args, dl_stream_t stream);
 /* out[r, j] = fl(fl(a s[r, j]) + fl(b z[r, j])) over n_rows x n_params (row strides lds_, ldz, ldo
  * >= n_params): dl_cheb_round's second line, so dl_mix_round into s and this call give the fused
  * round's bits -- the two-launch form, and the fallback where the round does not plan path 1.  out
