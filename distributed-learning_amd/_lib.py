@@ -133,6 +133,12 @@ class DlEdgeSqdistArgs(ctypes.Structure):
                 ("min_row_nnz", _i32)]
 
 
+class DlDenseRoundArgs(ctypes.Structure):
+    _fields_ = [("x", _vp), ("ldx", _i64), ("y", _vp), ("ldy", _i64), ("g", _vp), ("ldg", _i64),
+                ("lr", _f32), ("w", _vp), ("ldw", _i64), ("n_rows", _i32), ("n_params", _i64),
+                ("tile_cols", _i32)]
+
+
 class DlClipWeightsArgs(ctypes.Structure):
     _fields_ = [("W", DlCsr), ("edge_sq", _vp), ("tau", _vp), ("drop", _i32),
                 ("max_row_nnz", _i32), ("w_out", _vp), ("tau_out", _vp)]
@@ -252,6 +258,8 @@ SIGNATURES = {
     "dl_edge_sqdist_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "dl_edge_sqdist": (_i32, [ctypes.POINTER(DlEdgeSqdistArgs), _vp, _sz, _vp]),
     "dl_clip_weights": (_i32, [ctypes.POINTER(DlClipWeightsArgs), _vp]),
+    "dl_dense_round_plan": (_i32, [ctypes.POINTER(DlDenseRoundArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_dense_round": (_i32, [ctypes.POINTER(DlDenseRoundArgs), _vp]),
     "dl_axpby": (_i32, [_vp, _i64, _vp, _i64, _f32, _f32, _vp, _i64, _i32, _i64, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),

@@ -76,6 +76,9 @@ hipError_t launch_clip_weights(int n_rows, int nnz, int max_row_nnz, const int32
                                const int32_t *col, const float *w, const float *edge_sq,
                                const float *tau, int drop, float *w_out, float *tau_out,
                                hipStream_t s);
+// The dense round's kernel (mix_dense.hip) for one launch shaped by shape_dense_round: `grid`
+// workgroups of kDenseThreads with dense_lds_bytes(n_pad) of LDS
+hipError_t launch_mix_dense(const DenseArgs &a, int n_pad, bool fast, int grid, hipStream_t s);
 // out = fl(fl(a * s) + fl(b * z)) over n_rows x n_params (aux_kernels.hip); vec: float4 accesses
 hipError_t launch_axpby(const float *src, int64_t lds_, const float *z, int64_t ldz, float a,
                         float b, float *out, int64_t ldo, int n_rows, int64_t n_params, bool vec,

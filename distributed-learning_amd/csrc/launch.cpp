@@ -664,6 +664,119 @@ int shape_adam_round(const dl_adam_round_args *a, int n_cus, const Knobs &k, voi
     return DL_OK;
 }
 
+int shape_dense_round(const dl_dense_round_args *a, int n_cus, const Knobs &k, dl_mix_plan *plan,
+                      DenseLaunches *out, char *err) {
+    const char *who = "dl_dense_round";
+    if (!a) return fail(err, DL_ERR_INVALID, "%s: args is NULL", who);
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "%s_plan: plan is NULL", who);
+    if (!a->x || !a->y || !a->w) return fail(err, DL_ERR_INVALID, "%s: null x/y/w", who);
+    const int64_t N = a->n_rows, P = a->n_params, Tc = a->tile_cols;
+    if (N < 2 || N > kDenseMaxRows)
+        return fail(err, DL_ERR_INVALID, "%s: n_rows must be in 2..%d (got %d)", who,
+                    kDenseMaxRows, a->n_rows);
+    if (P <= 0)
+        return fail(err, DL_ERR_INVALID, "%s: n_params must be > 0 (got %lld)", who, (long long)P);
+    if (Tc < 0 || Tc % 16 || Tc > 4 * kMaxChunks)
+        return fail(err, DL_ERR_INVALID, "%s: tile_cols must be 0 or a multiple of 16 up to %d "
+                    "(got %d)", who, 4 * kMaxChunks, a->tile_cols);
+    if (a->ldw < N)
+        return fail(err, DL_ERR_INVALID, "%s: ldw %lld < n_rows %d", who, (long long)a->ldw,
+                    a->n_rows);
+    const bool tiled = Tc > 0;
+    const int64_t ntl = tiled ? (P + Tc - 1) / Tc : 0;
+    const struct { const char *name; const void *p; int64_t ld; } op[3] = {
+        {"ldx", a->x, a->ldx}, {"ldy", a->y, a->ldy}, {"ldg", a->g, a->ldg}};
+    size_t span[3] = {0, 0, 0};
+    for (int i = 0; i < 3; ++i) {
+        if (!op[i].p) continue;
+        const int64_t ld = op[i].ld;
+        if (tiled) {
+            if (ld != 0 && (ld < N || ld > 65535 * 4))
+                return fail(err, DL_ERR_INVALID, "%s: tiled ld: %s %lld is neither 0 nor n_rows "
+                            "%d .. 262140 block rows", who, op[i].name, (long long)ld, a->n_rows);
+            span[i] = (size_t)(((ntl - 1) * (ld ? ld : N) + N) * Tc * 4);
+        } else {
+            if (ld < P)
+                return fail(err, DL_ERR_INVALID, "%s: %s %lld < n_params %lld", who, op[i].name,
+                            (long long)ld, (long long)P);
+            span[i] = (size_t)((N - 1) * ld + P) * 4;
+        }
+    }
+    const size_t wspan = (size_t)((N - 1) * a->ldw + N) * 4;
+    if (overlaps(a->y, span[1], a->x, span[0]))
+        return fail(err, DL_ERR_INVALID, "%s: y overlaps x", who);
+    if (a->g && overlaps(a->y, span[1], a->g, span[2]))
+        return fail(err, DL_ERR_INVALID, "%s: y overlaps g", who);
+    if (overlaps(a->y, span[1], a->w, wspan))
+        return fail(err, DL_ERR_INVALID, "%s: y overlaps w", who);
+
+    const int np = dense_pad((int)N), tmax = dense_tmax(np);
+    const int64_t T = tiled ? Tc : tmax;                 // data tile
+    const int sub = (int)((T + tmax - 1) / tmax);
+    const int64_t n_data = (P + T - 1) / T;
+    // the float4 kernel reaches 16-byte aligned operands whose row offsets in a tile fit 32 bits
+    bool fast = true;
+    for (int i = 0; i < 3; ++i)
+        if (op[i].p)
+            fast = fast && aligned16(op[i].p) &&
+                   (tiled || (op[i].ld % 4 == 0 &&
+                              ((N - 1) * op[i].ld + tmax) * 4 < ((int64_t)1 << 32)));
+    const int64_t n_full = !fast ? 0 : tiled ? n_data * sub : P / tmax;   // kernel tiles
+    const int64_t n_tail = (tiled ? n_data * sub : n_data) - n_full;
+    const int64_t gmax = (int64_t)(n_cus > 0 ? n_cus : 1) * dense_wg_per_cu(np);
+    const int grid_full = (int)(n_full < gmax ? n_full : gmax);
+    const int grid_tail = (int)(n_tail < gmax ? n_tail : gmax);
+    if (plan) {
+        std::memset(plan, 0, sizeof *plan);
+        plan->path = kPathDense;
+        plan->tile_cols = (int32_t)T;
+        plan->grid = grid_full > 0 ? grid_full : grid_tail;
+        plan->lds_bytes = dense_lds_bytes(np);
+        plan->n_tiles = (int32_t)n_data;
+    }
+    if (!out) return DL_OK;
+    DenseArgs t;
+    std::memset(&t, 0, sizeof t);
+    t.x = a->x;
+    t.g = a->g;
+    t.y = a->y;
+    t.w = a->w;
+    t.ldw = a->ldw;
+    const int64_t ldg = a->g ? a->ldg : 0;
+    t.xts = tiled ? (a->ldx ? a->ldx : N) * T * 4 : T * 4;
+    t.gts = tiled ? (ldg ? ldg : N) * T * 4 : T * 4;
+    t.yts = tiled ? (a->ldy ? a->ldy : N) * T * 4 : T * 4;
+    t.xrs = tiled ? T * 4 : a->ldx * 4;
+    t.grs = tiled ? T * 4 : ldg * 4;
+    t.yrs = tiled ? T * 4 : a->ldy * 4;
+    t.col_end = tiled ? n_data * T : P;
+    t.n_rows = (int32_t)N;
+    t.tile_cols = (int32_t)T;
+    t.sub = sub;
+    t.lr = a->lr;
+    t.nt_load = k.nt_load;
+    t.nt_store = k.nt_store >= 0 ? k.nt_store : ((size_t)N * (size_t)P * 4 > kMallBytes ? 1 : 0);
+    out->n = 0;
+    out->n_pad = np;
+    if (grid_full > 0) {
+        auto &l = out->l[out->n++];
+        l.t = t;
+        l.t.tile0 = 0;
+        l.t.n_tiles = (int32_t)n_full;
+        l.grid = grid_full;
+        l.fast = true;
+    }
+    if (grid_tail > 0) {
+        auto &l = out->l[out->n++];
+        l.t = t;
+        l.t.tile0 = n_full;
+        l.t.n_tiles = (int32_t)n_tail;
+        l.grid = grid_tail;
+        l.fast = false;
+    }
+    return DL_OK;
+}
+
 int shape_trim_round(const dl_trim_round_args *a, int n_cus, const Knobs &k, void *ws,
                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
     if (!a) return fail(err, DL_ERR_INVALID, "dl_trim_round: args is NULL");

@@ -3,7 +3,8 @@
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
 // rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round,
-// dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist and their plan queries),
+// dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist, dl_dense_round and their plan
+// queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -198,6 +199,53 @@ constexpr int edge_slots(int max_nbrs) { return max_nbrs <= 4 ? 4 : max_nbrs <= 
 constexpr bool edge_slots_fit(int chunks, int n_rows, int max_nbrs) {
     return tile_passes(chunks, n_rows, true) * edge_slots(max_nbrs) <= kEdgeAccumulators;
 }
+
+// The dense round (mix_dense.hip), a kernel of its own: 512-thread workgroups, N padded to
+// dense_pad(N), kernel tiles of dense_tmax columns of all N rows in an LDS image of pitch
+// dense_pitch floats (= 16 mod 64: the four k groups of an MFMA fragment read on disjoint banks).
+constexpr int kDenseThreads = 512;
+constexpr int kDenseMaxRows = 256;
+constexpr int dense_pad(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : n <= 128 ? 128 : 256; }
+constexpr int dense_tmax(int n_pad) { return n_pad == 256 ? 64 : 128; }
+constexpr int dense_pitch(int n_pad) { return dense_tmax(n_pad) + 16; }
+constexpr int dense_lds_bytes(int n_pad) { return n_pad * dense_pitch(n_pad) * 4; }
+// workgroups a compute unit: two where the kernel fits 128 VGPRs and half the LDS
+constexpr int dense_wg_per_cu(int n_pad) { return n_pad <= 64 ? 2 : 1; }
+// The kernel's parameter.  Kernel tile kt of a launch is sub-tile (tile0 + kt) % sub of data tile
+// (tile0 + kt) / sub: TMAX columns at byte offset sub-tile x TMAX x 4 of the data tile (row-major:
+// tile_cols = TMAX, sub = 1, tile stride TMAX x 4).
+struct DenseArgs {
+    const float *x;
+    const float *g;       // nullable
+    float *y;
+    const float *w;       // dense row-major [n_rows][ldw]
+    int64_t ldw;
+    int64_t xts, gts, yts;   // data tile strides in bytes
+    int64_t xrs, grs, yrs;   // row strides in bytes (FAST: each row offset fits 32 bits)
+    int64_t tile0;           // first kernel tile of this launch
+    int64_t col_end;         // columns that exist (guarded kernel): n_params, or tiles x T
+    int32_t n_rows;
+    int32_t tile_cols;       // T: columns of a data tile, a multiple of 16
+    int32_t sub;             // kernel tiles a data tile: ceil(T / TMAX)
+    int32_t n_tiles;         // kernel tiles this launch walks
+    float lr;
+    int32_t nt_load, nt_store;   // as TileArgs'
+};
+struct DenseLaunches {
+    int32_t n, n_pad;
+    struct {
+        DenseArgs t;
+        int32_t grid;
+        bool fast;
+    } l[2];
+};
+// dl_dense_round / dl_dense_round_plan: every check, then whole aligned tiles on the FAST kernel
+// and a row-major ragged tail tile (or every tile of operands the FAST kernel cannot reach) on the
+// guarded one.  plan (nullable): path kPathDense, the data tiles, the first launch's grid.  out
+// NULL: the plan query, which needs `plan`.
+constexpr int32_t kPathDense = 6;
+int shape_dense_round(const dl_dense_round_args *a, int n_cus, const Knobs &k, dl_mix_plan *plan,
+                      DenseLaunches *out, char *err);
 
 // One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
 // launch_* functions of dl_internal.h take them.

@@ -480,6 +480,54 @@ def trim_round(W: DeviceCsr, X, Y, G=None, lr=0.0, trim=1, dev_sq=None, dev_max=
     return _fused_round_run("dl_trim_round", args, W, P, workspace)
 
 
+def _dense_round_args(Wd, X, Y, G, lr, tiled):
+    if Wd.dim() != 2 or Wd.shape[0] != Wd.shape[1] or Wd.dtype != torch.float32 or \
+            not Wd.is_cuda or Wd.stride(1) != 1:
+        raise ValueError(f"Wd must be a square row-major float32 device matrix (got "
+                         f"{tuple(Wd.shape)}, {Wd.dtype}, {Wd.device})")
+    n, dev = Wd.shape[0], Wd.device
+    if tiled is not None:
+        P, T = int(tiled[0]), int(tiled[1])
+        if T <= 0:
+            raise ValueError(f"dense_round: tile_cols must be > 0 in the tiled layout (got {T})")
+        ldx = _tiled_ld(X, "X", n, P, T, dev)
+        ldy = _tiled_ld(Y, "Y", n, P, T, dev)
+        ldg = _tiled_ld(G, "G", n, P, T, dev) if G is not None else 0
+    else:
+        P, T = X.shape[1], 0
+        _check(X, "X", n, P, dev)
+        _check(Y, "Y", n, P, dev)
+        if G is not None:
+            _check(G, "G", n, P, dev)
+        ldx, ldy, ldg = _ld(X), _ld(Y), _ld(G) if G is not None else 0
+    return _lib.DlDenseRoundArgs(_lib.ptr(X), ldx, _lib.ptr(Y), ldy, _lib.ptr(G), ldg, float(lr),
+                                 _lib.ptr(Wd), Wd.stride(0), n, P, T)
+
+
+def dense_round_plan(Wd, X, Y, G=None, tiled=None):
+    """dl_dense_round_plan: the configuration ``dense_round`` would run for these operands (path
+    6, the kernel's tile_cols, grid, n_tiles, lds_bytes)."""
+    lib = _lib.load()
+    args, plan = _dense_round_args(Wd, X, Y, G, 0.0, tiled), _lib.DlMixPlan()
+    _lib.check(lib.dl_dense_round_plan(ctypes.byref(args), ctypes.byref(plan)),
+               "dl_dense_round_plan")
+    return {f: getattr(plan, f) for f, _ in plan._fields_}
+
+
+def dense_round(Wd, X, Y, G=None, lr=0.0, tiled=None):
+    """One consensus round with a DENSE mixing matrix on the current stream (dl_dense_round):
+    Y = Wd (X - lr G) (X without G) on the fp32 matrix cores, each output the k-ordered fma chain
+    acc = fmaf(Wd[a][k], s_k, acc) from +0.0 over ALL k -- a zero weight takes part, so a
+    non-finite s_k reaches every row.  Wd: an N x N float32 device matrix, 2 <= N <= 256 (complete
+    graphs, powers and products of W, learned weights).  Y must not overlap X, G or Wd.
+    ``tiled=(n_params, tile_cols)``: X, G, Y in the column-tiled layout, tile_cols a multiple of
+    16.  No workspace and no deviation outputs (``deviation`` / ``deviation_tiled`` on Y)."""
+    lib = _lib.load()
+    args = _dense_round_args(Wd, X, Y, G, lr, tiled)
+    _lib.check(lib.dl_dense_round(ctypes.byref(args), _lib.stream_handle(Wd.device)),
+               "dl_dense_round")
+
+
 def _edge_sqdist_args(W, X, G, lr, out, tiled):
     # (the operands' checks of a round writing X in place; the pass itself writes no y)
     mix, _ = _fused_round_operands("edge_sqdist", None, W, X, X, G, lr, None, None, None, tiled,
@@ -1323,6 +1371,39 @@ class GossipEngine:
                           tiled=(self.P, self.T) if self.layout == "tiled" else None):
             raise RuntimeError(_lib.load().dl_last_error().decode())
         self.X, self.Y = self.Y, self.X
+
+    def round_dense(self, Wd, G=None, lr=0.0, deviation=False, mean=None):
+        """One round with the dense mixing matrix ``Wd`` (``dense_round``), X / Y ping-ponging as
+        in ``round``: X <- Wd (X - lr G) on the matrix cores, every output an fma chain over all N
+        agents in index order.  Wd is an N x N float32 device tensor in agent order -- a complete
+        graph's weights, ``dense_power(k)``, a product of time-varying W's; the engine's own CSR
+        plays no part.  G is in the resident layout.  With ``deviation`` (or ``mean``) the
+        existing ``deviation`` launch then runs on the new X: a second launch and a second read
+        of X, not a fused one.  ValueError under a row order (``order``: Wd would have to be
+        permuted) and for a Wd of the wrong shape, dtype or device."""
+        if self.order is not None:
+            raise ValueError("round_dense needs the agents in agent order: build the engine with "
+                             "order=None")
+        if not isinstance(Wd, torch.Tensor) or tuple(Wd.shape) != (self.n, self.n) or \
+                Wd.dtype != torch.float32 or Wd.device != self.device:
+            raise ValueError(f"Wd must be a float32 [{self.n}, {self.n}] tensor on {self.device}")
+        dense_round(Wd, self.X, self.Y, G, lr,
+                    tiled=(self.P, self.T) if self.layout == "tiled" else None)
+        self.X, self.Y = self.Y, self.X
+        if deviation or mean is not None:
+            self.deviation(mean_out=mean)
+
+    def dense_power(self, k):
+        """W^k as a dense float32 [N, N] device tensor: ``Csr.dense()`` of the engine's W raised
+        to the k-th power in float64 on the host and rounded once.  ``round_dense`` of it is k
+        gossip rounds in one pass (up to the rounding of the k folds it replaces)."""
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"dense_power needs k >= 0 (got {k})")
+        if self.W.n_src != self.n:
+            raise ValueError("dense_power needs a whole W (no halo rows)")
+        Wk = np.linalg.matrix_power(np.asarray(self.W.csr.dense(), np.float64), k)
+        return torch.as_tensor(Wk.astype(np.float32), device=self.device)
 
     def round_clip(self, G=None, lr=0.0, tau=None, drop=1, deviation=False, mean=None):
         """One clipped-gossip round (self-centred clipping; He, Karimireddy, Jaggi), X / Y

@@ -532,11 +532,16 @@ class MLPConsensusSGD:
     clip >= 1: clipped gossip instead (``GossipEngine.round_clip(drop=clip)``: W's weights kept,
     each agent's ``clip`` farthest neighbours pulled in to the distance of the next one), eager
     and under capture / replay.  Needs emit="grad"; exclusive with ``trim``, ``tracking``,
-    optimizer="adam", momentum and weight decay."""
+    optimizer="adam", momentum and weight decay.
+    dense=Wd: the round with the dense N x N float32 device matrix ``Wd`` instead of the engine's
+    sparse W (``GossipEngine.round_dense``: a complete graph, ``eng.dense_power(k)``, learned
+    weights), eager and under capture / replay; the deviation is then a launch of its own.  Needs
+    emit="grad"; exclusive with ``trim``, ``clip``, ``tracking``, optimizer="adam", momentum and
+    weight decay."""
 
     def __init__(self, ann, eng, data, labels, lr, deviation=True, emit="auto", sampler=None,
                  momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False, tracking=False,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, trim=0, clip=0):
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, trim=0, clip=0, dense=None):
         if eng.layout == "tiled" and ann.path != "fused":
             raise ValueError("the layered gradients read X row-major: use GossipEngine("
                              "layout='rows') or the fused kernel")
@@ -595,6 +600,11 @@ class MLPConsensusSGD:
         if self.clip and (self.trim or self.tracking or self.adam or momentum != 0.0 or
                           weight_decay != 0.0 or emit != "grad"):
             raise ValueError("clip needs emit='grad' and is exclusive with trim, tracking, "
+                             "optimizer='adam', momentum and weight_decay")
+        self.dense = dense
+        if dense is not None and (self.trim or self.clip or self.tracking or self.adam or
+                                  momentum != 0.0 or weight_decay != 0.0 or emit != "grad"):
+            raise ValueError("dense needs emit='grad' and is exclusive with trim, clip, tracking, "
                              "optimizer='adam', momentum and weight_decay")
         self.opt = dict(momentum=float(momentum), dampening=float(dampening),
                         weight_decay=float(weight_decay), nesterov=bool(nesterov))
@@ -700,6 +710,8 @@ class MLPConsensusSGD:
             self.eng.round_trim(self.G, self.lr, trim=self.trim, deviation=self.deviation)
         elif self.clip:
             self.eng.round_clip(self.G, self.lr, drop=self.clip, deviation=self.deviation)
+        elif self.dense is not None:
+            self.eng.round_dense(self.dense, self.G, self.lr, deviation=self.deviation)
         elif self.emit == "step":
             self.eng.round(src=self.G, deviation=self.deviation)
         else:

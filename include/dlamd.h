@@ -204,7 +204,8 @@ typedef struct dl_mix_plan {
                            CSR in registers (regular graphs of 5 entries per row whose CSR does
                            not fit LDS beside the tile), 5 = tile kernel with each row's first
                            entries in registers and the rest in LDS (irregular graphs with
-                           W.min_row_nnz >= 2 whose CSR does not fit LDS beside the tile) */
+                           W.min_row_nnz >= 2 whose CSR does not fit LDS beside the tile);
+                           6 = the dense matrix-core kernel (dl_dense_round_plan only) */
     int32_t tile_cols;  /* T: columns per tile (path 1) */
     int32_t grid;       /* workgroups launched */
     int32_t lds_bytes;  /* dynamic LDS per workgroup */
@@ -748,6 +749,51 @@ typedef struct dl_trim_round_args {
 int dl_trim_round_plan(const dl_trim_round_args *args, dl_mix_plan *plan);
 int dl_trim_round(const dl_trim_round_args *args, void *workspace, size_t ws_bytes,
                   dl_stream_t stream);
+/* One consensus round with a DENSE mixing matrix on the fp32 matrix cores (no reference
+ * counterpart: the reference's Mixer takes neighbour dicts).  For complete graphs, powers and
+ * products of W and learned N x N weights, whose CSR the LDS rounds cannot stage or fold at the
+ * HBM rate.  w is a device row-major N x N fp32 matrix, 2 <= N <= 256; for every column p:
+ *   s_j[p] = x_j[p]                          (g == NULL)
+ *   s_j[p] = fl(x_j[p] - fl(lr g_j[p]))      (g given: dl_mix_round's own step, two roundings)
+ *   acc    = +0.0f
+ *   acc    = fmaf(w[a][k], s_k[p], acc)      for k = 0 ... N-1, in that order
+ *   y_a[p] = acc
+ * -- the k-ordered fp32 fma chain of dl_bgemm.  Consequences of the rule:
+ *   Every w[a][k] takes part, a zero included: a non-finite s_k therefore reaches EVERY row as NaN
+ *     (the sparse rounds skip non-neighbours).
+ *   The sign of a sum that underflows to zero, and subnormal operands, are unspecified.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   tile_cols 0: x, g, y row-major with ldx / ldg / ldy >= n_params floats, any alignment
+ *     (16-byte aligned operands with ld % 4 == 0 take the float4 kernel, a ragged last tile and
+ *     everything else the guarded one: the same bits).  tile_cols T > 0: the column-tiled layout
+ *     [ceil(n_params/T)][rows][T] of dl_mix_args, T a multiple of 16, T <= 128; ld* are then the
+ *     ROWS of each operand's tiled blocks, 0 = n_rows.
+ *   y must not overlap x, g or w.  No deviation outputs: run dl_deviation(_tiled) on y.
+ *   DL_ERR_INVALID, each text naming the offending value: args NULL; x, y or w NULL ("null
+ *     x/y/w"); n_rows outside 2..256; n_params <= 0; tile_cols negative, not a multiple of 16 or
+ *     above 128; a row-major ld below n_params, ldw below n_rows, a tiled ld neither 0 nor >=
+ *     n_rows ("tiled ld"); y overlapping x, g or w ("y overlaps"); dl_dense_round_plan with plan
+ *     NULL.
+ *   No workspace, no allocation, no host synchronisation: capturable in a hipGraph.
+ * dl_dense_round_plan: DL_OK and path 6 (the dense kernel), tile_cols (the data tile; row-major:
+ * the kernel's own tile), n_tiles = ceil(n_params / tile_cols), the first launch's grid and the
+ * LDS bytes -- or the refusal, without touching the device. */
+typedef struct dl_dense_round_args {
+    const float *x;     /* [n_rows, ldx] */
+    int64_t ldx;
+    float *y;           /* [n_rows, ldy] */
+    int64_t ldy;
+    const float *g;     /* nullable [n_rows, ldg] */
+    int64_t ldg;
+    float lr;
+    const float *w;     /* device, row-major [n_rows, ldw] */
+    int64_t ldw;
+    int32_t n_rows;     /* N */
+    int64_t n_params;
+    int32_t tile_cols;  /* 0 = row-major */
+} dl_dense_round_args;
+int dl_dense_round_plan(const dl_dense_round_args *args, dl_mix_plan *plan);
+int dl_dense_round(const dl_dense_round_args *args, dl_stream_t stream);
 /* Per-edge squared distances in one HBM pass, and the clipped-gossip weights made from them (no
  * reference counterpart).  Clipped gossip (self-centred clipping; He, Karimireddy, Jaggi) is the
  * robust round that keeps W's weights: with s_a = x_a - lr g_a,
