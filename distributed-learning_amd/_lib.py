@@ -139,6 +139,21 @@ class DlDenseRoundArgs(ctypes.Structure):
                 ("tile_cols", _i32)]
 
 
+class DlBandRoundArgs(ctypes.Structure):
+    _fields_ = [("W", DlCsr), ("x", _vp), ("x_row_stride", _i64), ("x_tile_stride", _i64),
+                ("g", _vp), ("g_row_stride", _i64), ("g_tile_stride", _i64),
+                ("y", _vp), ("y_row_stride", _i64), ("y_tile_stride", _i64), ("lr", _f32),
+                ("n_params", _i64), ("tile_cols", _i32), ("n_blocks", _i32), ("n_segments", _i32),
+                ("block_row", _vp), ("seg_ptr", _vp), ("seg_row", _vp), ("seg_len", _vp),
+                ("slot", _vp), ("max_window_rows", _i32), ("max_block_rows", _i32),
+                ("max_slice_nnz", _i32)]
+
+
+class DlBandPlan(ctypes.Structure):
+    _fields_ = [("grid", _i32), ("lds_bytes", _i32), ("tile_cols", _i32),
+                ("rows_per_thread", _i32), ("n_items", _i64)]
+
+
 class DlClipWeightsArgs(ctypes.Structure):
     _fields_ = [("W", DlCsr), ("edge_sq", _vp), ("tau", _vp), ("drop", _i32),
                 ("max_row_nnz", _i32), ("w_out", _vp), ("tau_out", _vp)]
@@ -260,6 +275,9 @@ SIGNATURES = {
     "dl_clip_weights": (_i32, [ctypes.POINTER(DlClipWeightsArgs), _vp]),
     "dl_dense_round_plan": (_i32, [ctypes.POINTER(DlDenseRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_dense_round": (_i32, [ctypes.POINTER(DlDenseRoundArgs), _vp]),
+    "dl_band_lds_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "dl_band_round_plan": (_i32, [ctypes.POINTER(DlBandRoundArgs), ctypes.POINTER(DlBandPlan)]),
+    "dl_band_round": (_i32, [ctypes.POINTER(DlBandRoundArgs), _vp]),
     "dl_axpby": (_i32, [_vp, _i64, _vp, _i64, _f32, _f32, _vp, _i64, _i32, _i64, _vp]),
     "dl_mlp_workspace_bytes": (_sz, [_i32]),
     "dl_mlp_grad": (_i32, [ctypes.POINTER(DlMlpArgs), _vp]),

@@ -2,7 +2,7 @@
 // the environment knobs, read once per call.  What an entry point checks and launches is decided
 // by the host-only units -- the planner (plan.h) and the launch shaping (launch.h); here their
 // description of a call is turned into launch_* calls and the step after them.  Shaped there:
-// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist, dl_dense_round), the one-pass
+// the rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round, dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist, dl_dense_round, dl_band_round), the one-pass
 // deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch, dl_lenet_grad
 // and dl_lenet_eval.  The others (dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
 // deviation, the conversions, the step-rows functions, ...) check their own arguments here:
@@ -760,6 +760,35 @@ int dl_dense_round(const dl_dense_round_args *args, dl_stream_t stream) {
                                                   static_cast<hipStream_t>(stream));
         if (e != hipSuccess)
             return fail(DL_ERR_HIP, "mix_dense_kernel%s launch: %s (%d)",
+                        L.l[i].fast ? "" : " (guarded)", hipGetErrorString(e), (int)e);
+    }
+    return DL_OK;
+}
+
+size_t dl_band_lds_bytes(int32_t window_rows, int32_t tile_cols, int32_t block_rows,
+                         int32_t slice_nnz, int32_t shared_degree) {
+    return (size_t)dl::band_lds(window_rows, tile_cols, block_rows, slice_nnz, shared_degree).total;
+}
+
+int dl_band_round_plan(const dl_band_round_args *args, dl_band_plan *plan) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    if (!plan) return fail(DL_ERR_INVALID, "dl_band_round_plan: plan is NULL");
+    return status(dl::shape_band_round(args, device_cus(), dl::read_knobs(), plan, nullptr, err),
+                  err);
+}
+
+int dl_band_round(const dl_band_round_args *args, dl_stream_t stream) {
+    g_err.clear();
+    dl::BandLaunches L;
+    char err[dl::kErrLen];
+    const int rc = dl::shape_band_round(args, device_cus(), dl::read_knobs(), nullptr, &L, err);
+    if (rc) return status(rc, err);
+    for (int i = 0; i < L.n; ++i) {
+        const hipError_t e = dl::launch_mix_band(L.l[i].t, L.l[i].fast, L.l[i].grid, L.lds,
+                                                 static_cast<hipStream_t>(stream));
+        if (e != hipSuccess)
+            return fail(DL_ERR_HIP, "mix_band_kernel%s launch: %s (%d)",
                         L.l[i].fast ? "" : " (guarded)", hipGetErrorString(e), (int)e);
     }
     return DL_OK;

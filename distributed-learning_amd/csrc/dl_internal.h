@@ -79,6 +79,9 @@ hipError_t launch_clip_weights(int n_rows, int nnz, int max_row_nnz, const int32
 // The dense round's kernel (mix_dense.hip) for one launch shaped by shape_dense_round: `grid`
 // workgroups of kDenseThreads with dense_lds_bytes(n_pad) of LDS
 hipError_t launch_mix_dense(const DenseArgs &a, int n_pad, bool fast, int grid, hipStream_t s);
+// The banded round's kernel (mix_band.hip) for one launch shaped by shape_band_round: `grid`
+// persistent workgroups of kBandThreads with `lds` bytes of LDS (band_lds of the promises)
+hipError_t launch_mix_band(const BandArgs &a, bool fast, int grid, int lds, hipStream_t s);
 // out = fl(fl(a * s) + fl(b * z)) over n_rows x n_params (aux_kernels.hip); vec: float4 accesses
 hipError_t launch_axpby(const float *src, int64_t lds_, const float *z, int64_t ldz, float a,
                         float b, float *out, int64_t ldo, int n_rows, int64_t n_params, bool vec,

@@ -777,6 +777,148 @@ int shape_dense_round(const dl_dense_round_args *a, int n_cus, const Knobs &k, d
     return DL_OK;
 }
 
+int shape_band_round(const dl_band_round_args *a, int n_cus, const Knobs &k, dl_band_plan *plan,
+                     BandLaunches *out, char *err) {
+    const char *who = "dl_band_round";
+    if (!a) return fail(err, DL_ERR_INVALID, "%s: args is NULL", who);
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "%s_plan: plan is NULL", who);
+    if (!a->x || !a->y) return fail(err, DL_ERR_INVALID, "%s: null x/y", who);
+    if (!a->W.row_ptr || !a->W.w || !a->block_row || !a->seg_ptr || !a->seg_row || !a->seg_len ||
+        !a->slot)
+        return fail(err, DL_ERR_INVALID, "%s: null row_ptr/w or block table pointer", who);
+    const int64_t N = a->W.n_rows, P = a->n_params, T = a->tile_cols;
+    if (N < 1 || a->W.nnz < 1)
+        return fail(err, DL_ERR_INVALID, "%s: n_rows and nnz must be > 0 (got %d, %d)", who,
+                    a->W.n_rows, a->W.nnz);
+    if (P <= 0)
+        return fail(err, DL_ERR_INVALID, "%s: n_params must be > 0 (got %lld)", who, (long long)P);
+    if (!band_tile_ok(a->tile_cols))
+        return fail(err, DL_ERR_INVALID, "%s: tile_cols must be 4, 8, 16, 32, 64 or 128 (got %d)",
+                    who, a->tile_cols);
+    if (a->n_blocks < 1 || a->n_blocks > N || a->n_segments < 1)
+        return fail(err, DL_ERR_INVALID, "%s: n_blocks must be in 1..n_rows and n_segments > 0 "
+                    "(got %d, %d)", who, a->n_blocks, a->n_segments);
+    const bool shared = a->W.uniform_row_nnz > 0 && a->W.shared_row_weights;
+    if (a->W.uniform_row_nnz > 0 && (int64_t)a->W.uniform_row_nnz * N != a->W.nnz)
+        return fail(err, DL_ERR_INVALID, "%s: nnz %d != n_rows x uniform_row_nnz %d", who,
+                    a->W.nnz, a->W.uniform_row_nnz);
+    const BandLds L = band_lds(a->max_window_rows, a->tile_cols, a->max_block_rows,
+                               a->max_slice_nnz, shared ? a->W.uniform_row_nnz : 0);
+    if (L.total == 0 || L.total > kLdsBytes)
+        return fail(err, DL_ERR_INVALID, "%s: a window of %d rows x %d columns with a block of %d "
+                    "rows and %d entries exceeds the LDS budget of %d bytes", who,
+                    a->max_window_rows, a->tile_cols, a->max_block_rows, a->max_slice_nnz,
+                    kLdsBytes);
+    const int64_t ntl = (P + T - 1) / T;
+    // one layout kind for the three operands: row-major (tile stride T, rows of >= P floats) or
+    // column-tiled (row stride T, tiles of >= N rows)
+    const bool tiled = !(a->x_tile_stride == T && a->x_row_stride >= P);
+    const struct { const char *name; const void *p; int64_t rs, ts; } op[3] = {
+        {"x", a->x, a->x_row_stride, a->x_tile_stride},
+        {"y", a->y, a->y_row_stride, a->y_tile_stride},
+        {"g", a->g, a->g_row_stride, a->g_tile_stride}};
+    size_t span[3] = {0, 0, 0};
+    bool fast = true;
+    for (int i = 0; i < 3; ++i) {
+        if (!op[i].p) continue;
+        const bool ok = tiled ? op[i].rs == T && op[i].ts >= N * T && op[i].ts % T == 0
+                              : op[i].ts == T && op[i].rs >= P;
+        if (!ok)
+            return fail(err, DL_ERR_INVALID, "%s: strides of %s (row %lld, tile %lld) are not %s "
+                        "for %lld rows x %lld columns in tiles of %d", who, op[i].name,
+                        (long long)op[i].rs, (long long)op[i].ts,
+                        tiled ? "column-tiled" : "row-major", (long long)N, (long long)P,
+                        a->tile_cols);
+        span[i] = (size_t)(tiled ? (ntl - 1) * op[i].ts + N * T : (N - 1) * op[i].rs + P) * 4;
+        fast = fast && aligned16(op[i].p) && op[i].rs % 4 == 0 && op[i].ts % 4 == 0 &&
+               ((N - 1) * op[i].rs + T) * 4 < ((int64_t)1 << 32);
+    }
+    if (overlaps(a->y, span[1], a->x, span[0]))
+        return fail(err, DL_ERR_INVALID, "%s: y overlaps x", who);
+    if (a->g && overlaps(a->y, span[1], a->g, span[2]))
+        return fail(err, DL_ERR_INVALID, "%s: y overlaps g", who);
+
+    const int64_t n_full = !fast ? 0 : tiled ? ntl : P / T;
+    const int64_t n_tail = ntl - n_full;
+    // two workgroups' runs a CU where two LDS images fit (Knobs::wg_per_cu = 1: one)
+    const int64_t gmax = (int64_t)(n_cus > 0 ? n_cus : 1) *
+                         (2 * L.total <= kLdsBytes && k.wg_per_cu > 1 ? 2 : 1);
+    const int64_t items_full = n_full * a->n_blocks, items_tail = n_tail * a->n_blocks;
+    if (ntl > 0x7fffffff)
+        return fail(err, DL_ERR_INVALID, "%s: %lld tiles exceed the 32-bit tile count", who,
+                    (long long)ntl);
+    const int grid_full = (int)(items_full < gmax ? items_full : gmax);
+    const int grid_tail = (int)(items_tail < gmax ? items_tail : gmax);
+    int lc = 0;
+    while ((4 << lc) < T) ++lc;
+    if (plan) {
+        std::memset(plan, 0, sizeof *plan);
+        plan->grid = grid_full > 0 ? grid_full : grid_tail;
+        plan->lds_bytes = (int32_t)L.total;
+        plan->tile_cols = a->tile_cols;
+        plan->rows_per_thread = (int32_t)((((int64_t)a->max_window_rows << lc) + kBandThreads - 1) /
+                                          kBandThreads);
+        plan->n_items = items_full + items_tail;
+    }
+    if (!out) return DL_OK;
+    BandArgs t;
+    std::memset(&t, 0, sizeof t);
+    t.x = a->x;
+    t.g = a->g;
+    t.y = a->y;
+    t.xts = a->x_tile_stride * 4;
+    t.xrs = a->x_row_stride * 4;
+    t.gts = a->g ? a->g_tile_stride * 4 : 0;
+    t.grs = a->g ? a->g_row_stride * 4 : 0;
+    t.yts = a->y_tile_stride * 4;
+    t.yrs = a->y_row_stride * 4;
+    t.rowptr = a->W.row_ptr;
+    t.w = a->W.w;
+    t.block_row = a->block_row;
+    t.seg_ptr = a->seg_ptr;
+    t.seg_row = a->seg_row;
+    t.seg_len = a->seg_len;
+    t.slot = a->slot;
+    t.col_end = tiled ? ntl * T : P;
+    t.n_rows = (int32_t)N;
+    t.nnz = a->W.nnz;
+    t.n_blocks = a->n_blocks;
+    t.n_segments = a->n_segments;
+    t.log2c = lc;
+    t.degree = shared ? a->W.uniform_row_nnz : 0;
+    t.max_window = a->max_window_rows;
+    t.max_block = a->max_block_rows;
+    t.max_slice = a->max_slice_nnz;
+    t.map_off = (uint32_t)L.map_off;
+    t.w_off = (uint32_t)L.w_off;
+    t.slot_off = (uint32_t)L.slot_off;
+    t.rp_off = (uint32_t)L.rp_off;
+    t.lr = a->lr;
+    t.nt_load = k.nt_load;
+    t.nt_store = k.nt_store >= 0 ? k.nt_store : ((size_t)N * (size_t)P * 4 > kMallBytes ? 1 : 0);
+    out->n = 0;
+    out->lds = (int32_t)L.total;
+    if (grid_full > 0) {
+        auto &l = out->l[out->n++];
+        l.t = t;
+        l.t.tile0 = 0;
+        l.t.n_tiles = (int32_t)n_full;
+        l.t.n_items = items_full;
+        l.grid = grid_full;
+        l.fast = true;
+    }
+    if (grid_tail > 0) {
+        auto &l = out->l[out->n++];
+        l.t = t;
+        l.t.tile0 = n_full;
+        l.t.n_tiles = (int32_t)n_tail;
+        l.t.n_items = items_tail;
+        l.grid = grid_tail;
+        l.fast = false;
+    }
+    return DL_OK;
+}
+
 int shape_trim_round(const dl_trim_round_args *a, int n_cus, const Knobs &k, void *ws,
                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
     if (!a) return fail(err, DL_ERR_INVALID, "dl_trim_round: args is NULL");

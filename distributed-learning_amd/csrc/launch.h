@@ -3,8 +3,8 @@
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
 // rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round,
-// dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist, dl_dense_round and their plan
-// queries),
+// dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist, dl_dense_round, dl_band_round and
+// their plan queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -246,6 +246,75 @@ struct DenseLaunches {
 constexpr int32_t kPathDense = 6;
 int shape_dense_round(const dl_dense_round_args *a, int n_cus, const Knobs &k, dl_mix_plan *plan,
                       DenseLaunches *out, char *err);
+
+// The banded round (mix_band.hip), a kernel of its own: persistent 1024-thread workgroups walk
+// (block of consecutive rows, tile of 4C columns) items; a workgroup's LDS holds the block's
+// window image [window rows][C] float4, the window's row map, and the block's CSR slice: weights,
+// u16 window slots and u16 row pointers -- or, with shared row weights (degree > 0), one weight
+// sequence and the slots alone (2 B an entry: 10 B a row on a torus).
+constexpr int kBandThreads = kTileThreads;
+constexpr int kBandPrefetch = 4;    // staging passes a thread holds in registers one item ahead
+constexpr bool band_tile_ok(int T) {
+    return T == 4 || T == 8 || T == 16 || T == 32 || T == 64 || T == 128;
+}
+struct BandLds {
+    int64_t map_off, w_off, slot_off, rp_off;   // byte offsets behind the image
+    int64_t total;                              // 0: sizes the kernel does not serve
+};
+// THE budget: graph.band_blocks grows its blocks against it (through dl_band_lds_bytes) and
+// shape_band_round lays the kernel's LDS out by it, from the promised maxima.
+constexpr BandLds band_lds(int64_t window_rows, int tile_cols, int64_t block_rows,
+                           int64_t slice_nnz, int shared_degree) {
+    if (!band_tile_ok(tile_cols) || window_rows < 1 || block_rows < 1 || slice_nnz < 1 ||
+        window_rows > 65535 || slice_nnz > 65535 || block_rows > 65535 || shared_degree < 0)
+        return {0, 0, 0, 0, 0};
+    const auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
+    const int64_t map_off = window_rows * tile_cols * 4;
+    const int64_t w_off = map_off + up(4 * window_rows);
+    const int64_t slot_off = w_off + up(4 * (shared_degree > 0 ? shared_degree : slice_nnz));
+    const int64_t rp_off = slot_off + up(2 * slice_nnz);
+    return {map_off, w_off, slot_off, rp_off,
+            rp_off + (shared_degree > 0 ? 0 : up(2 * (block_rows + 1)))};
+}
+// The kernel's parameter.  Item i of a launch is block i / n_tiles, tile tile0 + i % n_tiles;
+// workgroup k walks the k-th of gridDim.x equal contiguous runs of items, so a run stays in one
+// block while its tiles last.  Element (row r, tile t, chunk c) of x is at byte t xts + r xrs +
+// 16 c (FAST: r xrs + 16 c fits 32 bits).
+struct BandArgs {
+    const float *x;
+    const float *g;       // nullable
+    float *y;
+    int64_t xts, gts, yts;   // tile strides in bytes
+    int64_t xrs, grs, yrs;   // row strides in bytes
+    const int32_t *rowptr;   // W
+    const float *w;
+    const int32_t *block_row, *seg_ptr, *seg_row, *seg_len;   // dl_band_round_args' table
+    const uint16_t *slot;
+    int64_t tile0;           // first tile of this launch
+    int64_t n_items;         // n_blocks x n_tiles
+    int64_t col_end;         // columns that exist (guarded kernel)
+    int32_t n_rows, nnz, n_blocks, n_segments;
+    int32_t n_tiles;         // tiles this launch walks
+    int32_t log2c;           // C = 1 << log2c float4 chunks a tile row
+    int32_t degree;          // shared row weights: entries a row; 0: the general slice
+    int32_t max_window, max_block, max_slice;   // the promises: every table value is clamped
+    uint32_t map_off, w_off, slot_off, rp_off;  // band_lds of the promises
+    float lr;
+    int32_t nt_load, nt_store;   // as TileArgs'
+};
+struct BandLaunches {
+    int32_t n, lds;
+    struct {
+        BandArgs t;
+        int32_t grid;
+        bool fast;
+    } l[2];
+};
+// dl_band_round / dl_band_round_plan: every check, then whole aligned tiles on the FAST kernel and
+// a row-major ragged last tile (or every tile of operands the FAST kernel cannot reach) on the
+// guarded one.  out NULL: the plan query, which needs `plan`.
+int shape_band_round(const dl_band_round_args *a, int n_cus, const Knobs &k, dl_band_plan *plan,
+                     BandLaunches *out, char *err);
 
 // One kernel launch.  `t` is the kernel's parameter; the selectors pick the instantiation as the
 // launch_* functions of dl_internal.h take them.

@@ -528,6 +528,73 @@ def dense_round(Wd, X, Y, G=None, lr=0.0, tiled=None):
                "dl_dense_round")
 
 
+class DeviceBand:
+    """A ``graph.BandPlan`` uploaded to the device (the block table of dl_band_round_args)."""
+
+    def __init__(self, plan, device):
+        self.plan = plan
+        self.device = torch.device(device)
+        self.block_row, self.seg_ptr, self.seg_row, self.seg_len = (
+            torch.as_tensor(np.ascontiguousarray(a, np.int32), device=self.device)
+            for a in (plan.block_row, plan.seg_ptr, plan.seg_row, plan.seg_len))
+        # (u16 slots travel as an int16 tensor of the same bits)
+        self.slot = torch.as_tensor(np.ascontiguousarray(plan.slot, np.uint16).view(np.int16),
+                                    device=self.device)
+
+
+def _band_round_args(W, band, X, Y, G, lr, tiled):
+    n, dev, T = W.n_rows, W.device, band.plan.tile_cols
+    if W.n_src != n:
+        raise ValueError("band_round needs a whole W (no halo rows)")
+    if band.slot.numel() != W.nnz or band.device != dev:
+        raise ValueError(f"the band plan has {band.slot.numel()} slots on {band.device}, W has "
+                         f"{W.nnz} entries on {dev}")
+    ops = []
+    if tiled is not None:
+        P = int(tiled[0])
+        if int(tiled[1]) != T:
+            raise ValueError(f"band_round: the operands' tile_cols {tiled[1]} is not the band "
+                             f"plan's {T}")
+        for t, name in ((X, "X"), (G, "G"), (Y, "Y")):
+            ops += [_lib.ptr(t), T, _tiled_ld(t, name, n, P, T, dev) * T] if t is not None \
+                else [None, 0, 0]
+    else:
+        P = X.shape[1]
+        for t, name in ((X, "X"), (G, "G"), (Y, "Y")):
+            if t is not None:
+                _check(t, name, n, P, dev)
+            ops += [_lib.ptr(t), _ld(t), T] if t is not None else [None, 0, 0]
+    p = band.plan
+    return _lib.DlBandRoundArgs(W.c_struct(), *ops, float(lr), P, T, p.blocks,
+                                len(p.seg_row), _lib.ptr(band.block_row), _lib.ptr(band.seg_ptr),
+                                _lib.ptr(band.seg_row), _lib.ptr(band.seg_len),
+                                _lib.ptr(band.slot), p.max_window_rows, p.max_block_rows,
+                                p.max_slice_nnz)
+
+
+def band_round_plan(W: DeviceCsr, band: DeviceBand, X, Y, G=None, tiled=None):
+    """dl_band_round_plan: the configuration ``band_round`` would run for these operands (grid,
+    lds_bytes, tile_cols, rows_per_thread, n_items)."""
+    lib = _lib.load()
+    args, plan = _band_round_args(W, band, X, Y, G, 0.0, tiled), _lib.DlBandPlan()
+    _lib.check(lib.dl_band_round_plan(ctypes.byref(args), ctypes.byref(plan)),
+               "dl_band_round_plan")
+    return {f: getattr(plan, f) for f, _ in plan._fields_}
+
+
+def band_round(W: DeviceCsr, band: DeviceBand, X, Y, G=None, lr=0.0, tiled=None):
+    """One consensus round on the current stream through LDS windows (dl_band_round): Y = W (X -
+    lr G) (X without G) with ``mix_round``'s bits, for a W of ANY row count whose rows
+    ``graph.band_blocks`` could cut into blocks with narrow windows (``band`` = DeviceBand of that
+    plan).  Y must not overlap X or G.  ``tiled=(n_params, tile_cols)``: X, G, Y in the
+    column-tiled layout, tile_cols the band plan's; row-major tensors otherwise (any ld).  No
+    workspace and no deviation outputs (``deviation`` / ``deviation_tiled`` on Y)."""
+    lib = _lib.load()
+    args = _band_round_args(W, band, X, Y, G, lr, tiled)
+    _lib.check(lib.dl_band_round(ctypes.byref(args), _lib.stream_handle(W.device)),
+               "dl_band_round")
+
+
 def _edge_sqdist_args(W, X, G, lr, out, tiled):
     # (the operands' checks of a round writing X in place; the pass itself writes no y)
     mix, _ = _fused_round_operands("edge_sqdist", None, W, X, X, G, lr, None, None, None, tiled,
@@ -1141,13 +1208,19 @@ class GossipEngine:
     """
 
     def __init__(self, csr: Csr, n_params, device="cuda", X=None, layout="auto", tile_cols=None,
-                 order="auto"):
+                 order="auto", band=None):
         """order (optional, ``graph.lds_slot_order``): order[slot] = agent, the row order of the
         resident matrices.  ``load_rows`` / ``layout_like`` / ``rows`` take and return agent
         order; ``dev_sq`` is per slot (``agent_dev_sq()`` in agent order).  "auto": the agents
         by descending row length (``graph.row_length_order``) when the round runs the
         register-head + LDS-tail kernel (plan path 5, irregular graphs of thousands of agents),
-        else agent order (None)."""
+        else agent order (None).
+        band (optional, ``graph.band_blocks`` of the csr in its resident row order): the block
+        table of ``round_band``.  With it, layout="tiled" at the plan's tile_cols is admitted for
+        graphs that do not fit the LDS tile kernel (``round`` is then the gather kernel's and
+        takes row-major operands only: use ``round_band``); "auto" order is agent order."""
+        if band is not None and isinstance(order, str) and order == "auto":
+            order = None
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -1170,15 +1243,25 @@ class GossipEngine:
             self.order = torch.as_tensor(order, device=self.device)
         self.W = DeviceCsr(csr, self.device)
         self.n, self.P = csr.n_rows, int(n_params)
-        plan = plan_shape(self.W, self.P, deviation=True,
-                          tile_cols=int(tile_cols) if tile_cols else -1)
+        self._band = None       # DeviceBand of round_band: from `band`, or built on first use
+        band_tiled = band is not None and layout == "tiled" and tile_cols and \
+            int(tile_cols) == band.tile_cols and self.W.n_src == self.n
+        try:
+            plan = plan_shape(self.W, self.P, deviation=True,
+                              tile_cols=int(tile_cols) if tile_cols else -1)
+        except ValueError:      # tile_cols does not fit the tile kernel
+            if not band_tiled:
+                raise
+            plan = {"path": 2, "tile_cols": 0, "head": 0}
         if plan["path"] == 5:
             self.W.hub_rows = hub_rows(csr, plan["head"])
         tiled_ok = plan["path"] in (1, 4, 5) and plan["tile_cols"] >= 4 and self.W.n_src == self.n
         if layout == "auto":
             layout = "tiled" if tiled_ok else "rows"
-        if layout == "tiled" and not tiled_ok:
+        if layout == "tiled" and not tiled_ok and not band_tiled:
             raise ValueError("this graph does not fit the LDS tile kernel; use layout='rows'")
+        if band is not None:
+            self._band = DeviceBand(band, self.device)
         self.layout = layout
         self.T = (int(tile_cols) if tile_cols else plan["tile_cols"]) if layout == "tiled" else 0
         self.dev_sq = torch.zeros(self.n, dtype=torch.float32, device=self.device)
@@ -1404,6 +1487,35 @@ class GossipEngine:
             raise ValueError("dense_power needs a whole W (no halo rows)")
         Wk = np.linalg.matrix_power(np.asarray(self.W.csr.dense(), np.float64), k)
         return torch.as_tensor(Wk.astype(np.float32), device=self.device)
+
+    @property
+    def band_plan(self):
+        """The ``graph.BandPlan`` of ``round_band`` (blocks, max_window_rows, amplification, ...):
+        the one given at construction, else ``graph.band_blocks`` of the resident CSR at the
+        layout's tile width (16 columns row-major), built on first use.  ValueError when the graph
+        has no locality in its row order (``graph.bfs_order``)."""
+        if self._band is None:
+            from .graph import band_blocks
+            self._band = DeviceBand(band_blocks(self.W.csr, tile_cols=self.T or 16), self.device)
+        return self._band.plan
+
+    def round_band(self, G=None, lr=0.0, deviation=False, mean=None):
+        """One round through LDS windows (``band_round``), X / Y ping-ponging as in ``round`` and
+        with its bits: X <- W (X - lr G), G in the resident layout.  For graphs with locality at
+        ANY agent count -- beyond 8192 agents ``round`` is the gather kernel's.  Row-major at any
+        N; column-tiled when the engine was built with ``band=`` and its tile_cols.  The
+        deviation is not fused (a block does not see all agents): with ``deviation`` (or ``mean``)
+        the ``deviation`` launch then runs on the new X (column-tiled beyond the tile kernel's
+        agent count ``dl_deviation_tiled`` refuses: measure ``rows()`` there)."""
+        plan = self.band_plan
+        if self.layout == "tiled" and self.T != plan.tile_cols:
+            raise ValueError(f"round_band: the resident tiles have {self.T} columns, the band "
+                             f"plan's {plan.tile_cols}")
+        band_round(self.W, self._band, self.X, self.Y, G, lr,
+                   tiled=(self.P, self.T) if self.layout == "tiled" else None)
+        self.X, self.Y = self.Y, self.X
+        if deviation or mean is not None:
+            self.deviation(mean_out=mean)
 
     def round_clip(self, G=None, lr=0.0, tau=None, drop=1, deviation=False, mean=None):
         """One clipped-gossip round (self-centred clipping; He, Karimireddy, Jaggi), X / Y

@@ -452,6 +452,101 @@ def row_length_order(csr):
     return np.argsort(-np.diff(csr.rowptr), kind="stable")
 
 
+def bfs_order(csr, start=0):
+    """Agents in breadth-first order from ``start`` (order[slot] = agent, neighbours in CSR entry
+    order, further components after the first): a scattered numbering of a graph with locality
+    becomes banded, which ``band_blocks`` needs.  For ``GossipEngine(order=...)`` / ``permuted``."""
+    n = csr.n_rows
+    seen = np.zeros(n, bool)
+    order = []
+    for root in [start] + list(range(n)):
+        if seen[root]:
+            continue
+        seen[root] = True
+        queue, head = [root], 0
+        while head < len(queue):
+            a = queue[head]
+            head += 1
+            for j in csr.col[csr.rowptr[a]:csr.rowptr[a + 1]].tolist():
+                if not seen[j]:
+                    seen[j] = True
+                    queue.append(j)
+        order.extend(queue)
+    return np.asarray(order, np.int64)
+
+
+@dataclass
+class BandPlan:
+    """Block table of the banded round (include/dlamd.h dl_band_round_args), host arrays."""
+    block_row: np.ndarray    # int32 [blocks + 1]: block b = rows [block_row[b], block_row[b+1])
+    seg_ptr: np.ndarray      # int32 [blocks + 1]: block b's window = segments [seg_ptr[b], ...)
+    seg_row: np.ndarray      # int32 [segments]: first global row of a segment
+    seg_len: np.ndarray      # int32 [segments]: its rows
+    slot: np.ndarray         # uint16 [nnz]: position of col[e] in its block's window
+    tile_cols: int
+    max_window_rows: int
+    max_block_rows: int
+    max_slice_nnz: int
+    amplification: float     # sum of the windows' rows / N: x and g are read this many times
+
+    @property
+    def blocks(self):
+        return len(self.block_row) - 1
+
+
+def band_blocks(csr, max_window_rows=None, tile_cols=16, max_amplification=2.0):
+    """Cut the rows of ``csr`` into consecutive blocks for the banded round.  A block's window is
+    the sorted union of the columns its rows reference, stored as segments of consecutive rows (a
+    ring's or torus's wrap-around is a second or third segment); every CSR entry gets the u16
+    position of its source row in its block's window.  Blocks grow greedily while the window has
+    at most ``max_window_rows`` rows (None: no cap) and window, row map and CSR slice fit the
+    kernel's LDS budget at ``tile_cols`` columns a tile (dl_band_lds_bytes <= 160 KiB).  ValueError
+    when a single row does not fit, or when the read amplification (sum of window rows / N)
+    exceeds ``max_amplification``: the graph has no locality in this numbering (``bfs_order``), or
+    none at all, and stays on ``dl_mix_round``."""
+    from . import _lib
+    budget = _lib.load().dl_band_lds_bytes
+    if csr.n_src != csr.n_rows:
+        raise ValueError("band_blocks needs a whole W (no halo rows)")
+    n, rp = csr.n_rows, csr.rowptr
+    cap = 65535 if max_window_rows is None else int(max_window_rows)
+    shared = csr.uniform_row_nnz if csr.shared_row_weights else 0
+    cols = csr.col.tolist()
+    block_row, seg_ptr, seg_row, seg_len = [0], [0], [], []
+    slot = np.empty(csr.nnz, np.uint16)
+    r0 = 0
+    while r0 < n:
+        win, r = set(), r0
+        while r < n:
+            new = {j for j in cols[rp[r]:rp[r + 1]] if j not in win}
+            rows, nnz, nw = r + 1 - r0, int(rp[r + 1] - rp[r0]), len(win) + len(new)
+            need = budget(max(nw, 1), int(tile_cols), rows, max(nnz, 1), shared)
+            if nw > cap or need == 0 or need > 160 * 1024:
+                break
+            win |= new
+            r += 1
+        if r == r0:
+            raise ValueError(f"row {r0} alone ({rp[r0 + 1] - rp[r0]} entries) does not fit a "
+                             f"window of {cap} rows x {tile_cols} columns in LDS")
+        w = np.fromiter(sorted(win), np.int64, len(win))
+        first = np.flatnonzero(np.diff(w, prepend=w[:1] - 2) != 1) if len(w) else w
+        seg_row.extend(w[first].tolist())
+        seg_len.extend(np.diff(np.append(first, len(w))).tolist())
+        seg_ptr.append(len(seg_row))
+        slot[rp[r0]:rp[r]] = np.searchsorted(w, csr.col[rp[r0]:rp[r]])
+        block_row.append(r)
+        r0 = r
+    i32 = lambda v: np.asarray(v, np.int32)   # noqa: E731
+    windows = np.diff(np.concatenate([[0], np.cumsum(seg_len)])[seg_ptr])
+    plan = BandPlan(i32(block_row), i32(seg_ptr), i32(seg_row), i32(seg_len), slot, int(tile_cols),
+                    int(windows.max()), int(np.diff(block_row).max()),
+                    int(np.diff(rp[block_row]).max()), float(windows.sum()) / n)
+    if plan.amplification > max_amplification:
+        raise ValueError(f"windows of {cap} rows read x {plan.amplification:.2f} times (bound "
+                         f"{max_amplification}): no locality in this numbering")
+    return plan
+
+
 def permuted(csr, order):
     """The CSR of the same W with rows stored in slot order (row s = agent order[s]); every row
     keeps its entry order, so the fp32 fold of each agent is unchanged."""

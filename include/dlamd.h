@@ -794,6 +794,79 @@ typedef struct dl_dense_round_args {
 } dl_dense_round_args;
 int dl_dense_round_plan(const dl_dense_round_args *args, dl_mix_plan *plan);
 int dl_dense_round(const dl_dense_round_args *args, dl_stream_t stream);
+/* One consensus round of a sparse W with LOCALITY from LDS windows, for graphs whose column tile
+ * of all agents does not fit one workgroup's LDS (more than 8192 agents: large tori, rings,
+ * geometric graphs; dl_mix_round takes the gather kernel there).  No reference counterpart beyond
+ * dl_mix_round's own (Mixer._mix_params_once), whose rule and bits it keeps:
+ *   t_j[p] = x_j[p], or fl(x_j[p] - fl(lr g_j[p])) with g;
+ *   acc = +0.0f;  acc = fl(acc + fl(w_e t_col(e)[p])) over row a's entries in CSR order;
+ *   y_a[p] = acc.
+ * The rows are cut into n_blocks blocks of consecutive rows (block b = rows [block_row[b],
+ * block_row[b+1])).  A block's window is the sorted union of the columns its rows reference,
+ * stored as segments of consecutive rows: segments [seg_ptr[b], seg_ptr[b+1]) of the block, segment
+ * i = rows [seg_row[i], seg_row[i] + seg_len[i]) -- a ring's or torus's wrap-around is a second or
+ * third segment.  slot[e] is, for CSR entry e, the position of col[e] in its block's window (the
+ * kernel never searches).  A workgroup stages one window x 4C columns in LDS beside the block's
+ * CSR slice and folds the block's rows from LDS.  graph.band_blocks builds the table.
+ *   Layouts, by two strides per operand (in floats): element (row r, column p) of x is
+ *     x[(p / T) * x_tile_stride + r * x_row_stride + p % T], T = tile_cols.  Row-major [N][ld]:
+ *     row stride ld >= n_params, tile stride T.  Column-tiled [ceil(P/T)][rows][T] (last tile
+ *     zero-padded): row stride T, tile stride rows x T, rows >= n_rows.  x, g and y share the
+ *     layout kind.  16-byte aligned operands with strides that are multiples of 4 and row offsets
+ *     below 4 GiB take the float4 kernel; a ragged last row-major tile and everything else the
+ *     guarded one (the same bits), which reads columns past n_params as zero and never writes them.
+ *   tile_cols: 4, 8, 16, 32, 64 or 128.
+ *   Promises: max_window_rows >= every block's window, max_block_rows >= every block's rows,
+ *     max_slice_nnz >= every block's CSR entries.  They size the LDS: dl_band_lds_bytes of them
+ *     must be at most 160 KiB.  The kernel clamps what it reads from the table to the promises
+ *     and to W's sizes, so a wrong table gives wrong, never out-of-bounds, results.
+ *   W: square (n_halo rows do not exist here), any row count the int32 CSR holds.  With
+ *     uniform_row_nnz > 0 and shared_row_weights the slice is staged without row pointers and with
+ *     one weight sequence (2 bytes an entry).
+ *   y must not overlap x or g: other blocks read x's window rows after a block has written.
+ *   No deviation outputs: a block does not see all agents.  Run dl_deviation(_tiled) on y.
+ *   DL_ERR_INVALID, each text naming the offending value: args NULL; null x / y / table pointers;
+ *     n_rows, n_params, n_blocks, n_segments < 1; tile_cols not one of the six; strides that are
+ *     neither layout ("strides"); promises < 1 or beyond the LDS budget ("LDS budget"); y
+ *     overlapping x or g ("y overlaps"); dl_band_round_plan with plan NULL.
+ *   No workspace, no allocation, no host synchronisation: capturable in a hipGraph.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged. */
+typedef struct dl_band_round_args {
+    dl_csr W;
+    const float *x;
+    int64_t x_row_stride, x_tile_stride;
+    const float *g;              /* nullable */
+    int64_t g_row_stride, g_tile_stride;
+    float *y;
+    int64_t y_row_stride, y_tile_stride;
+    float lr;
+    int64_t n_params;
+    int32_t tile_cols;           /* T = 4C */
+    int32_t n_blocks;
+    int32_t n_segments;
+    const int32_t *block_row;    /* device [n_blocks + 1] */
+    const int32_t *seg_ptr;      /* device [n_blocks + 1] */
+    const int32_t *seg_row;      /* device [n_segments] */
+    const int32_t *seg_len;      /* device [n_segments] */
+    const uint16_t *slot;        /* device [W.nnz] */
+    int32_t max_window_rows;
+    int32_t max_block_rows;
+    int32_t max_slice_nnz;
+} dl_band_round_args;
+typedef struct dl_band_plan {
+    int32_t grid;            /* persistent workgroups of the first launch */
+    int32_t lds_bytes;       /* dynamic LDS per workgroup */
+    int32_t tile_cols;
+    int32_t rows_per_thread; /* staging passes of the longest window: ceil(rows x C / 1024) */
+    int64_t n_items;         /* (block, tile) work items of the round */
+} dl_band_plan;
+/* LDS bytes of a workgroup for these promises -- the budget graph.band_blocks grows its blocks
+ * against (<= 160 KiB) -- or 0 for sizes the kernel does not serve (tile_cols, > 65535 window
+ * rows or slice entries).  shared_degree: W.uniform_row_nnz when W.shared_row_weights, else 0. */
+size_t dl_band_lds_bytes(int32_t window_rows, int32_t tile_cols, int32_t block_rows,
+                         int32_t slice_nnz, int32_t shared_degree);
+int dl_band_round_plan(const dl_band_round_args *args, dl_band_plan *plan);
+int dl_band_round(const dl_band_round_args *args, dl_stream_t stream);
 /* Per-edge squared distances in one HBM pass, and the clipped-gossip weights made from them (no
  * reference counterpart).  Clipped gossip (self-centred clipping; He, Karimireddy, Jaggi) is the
  * robust round that keeps W's weights: with s_a = x_a - lr g_a,
