@@ -105,6 +105,11 @@ class DlChebRoundArgs(ctypes.Structure):
     _fields_ = [("mix", DlMixArgs), ("z", _vp), ("ldz", _i64), ("a", _f32), ("b", _f32)]
 
 
+class DlChebRoundsArgs(ctypes.Structure):
+    _fields_ = [("mix", DlMixArgs), ("z", _vp), ("ldz", _i64), ("z_out", _vp), ("ldzo", _i64),
+                ("coef", _vp), ("rounds", _i32), ("trace", _vp)]
+
+
 class DlTrackRoundArgs(ctypes.Structure):
     _fields_ = [("mix", DlMixArgs), ("d", _vp), ("ldd", _i64), ("d_out", _vp), ("lddo", _i64),
                 ("g_old", _vp), ("ldq", _i64)]
@@ -261,6 +266,9 @@ SIGNATURES = {
     "dl_sgd_round": (_i32, [ctypes.POINTER(DlSgdRoundArgs), _vp, _sz, _vp]),
     "dl_cheb_round_plan": (_i32, [ctypes.POINTER(DlChebRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_cheb_round": (_i32, [ctypes.POINTER(DlChebRoundArgs), _vp, _sz, _vp]),
+    "dl_cheb_rounds_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dl_cheb_rounds_plan": (_i32, [ctypes.POINTER(DlChebRoundsArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_cheb_rounds": (_i32, [ctypes.POINTER(DlChebRoundsArgs), _vp, _sz, _vp]),
     "dl_track_round_plan": (_i32, [ctypes.POINTER(DlTrackRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_track_round": (_i32, [ctypes.POINTER(DlTrackRoundArgs), _vp, _sz, _vp]),
     "dl_adam_tick": (_i32, [_vp, _vp]),

@@ -166,6 +166,10 @@ int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, cons
                 e = dl::launch_mix_multi(l.t, l.chunks, l.rounds, l.sgd, l.dev, l.grid, l.lds, s);
                 who = "mix_multi_kernel launch";
                 break;
+            case dl::kLaunchChebMulti:
+                e = dl::launch_mix_cheb_multi(l.t, l.m, l.chunks, l.rounds, l.out, l.grid, l.lds, s);
+                who = "mix_cheb_multi_kernel launch";
+                break;
             case dl::kLaunchTrace:
                 e = dl::launch_mix_trace(l.t, l.chunks, l.planes, l.rounds, l.grid, l.lds, trace,
                                          s);
@@ -728,6 +732,22 @@ int dl_cheb_round_plan(const dl_cheb_round_args *args, dl_mix_plan *plan) {
 int dl_cheb_round(const dl_cheb_round_args *args, void *workspace, size_t ws_bytes,
                   dl_stream_t stream) {
     return fused_round(dl::shape_cheb_round, "mix_cheb_tile_kernel", args, workspace, ws_bytes,
+                       stream);
+}
+
+size_t dl_cheb_rounds_workspace_bytes(int32_t n_rows, int32_t rounds, int32_t trace) {
+    if (n_rows <= 0 || rounds <= 0) return 0;
+    const int parts = dl::max_parts(device_cus(), dl::read_knobs());
+    return dl::cheb_rounds_workspace_bytes(parts, n_rows, rounds, trace != 0, true) + kAlign;
+}
+
+int dl_cheb_rounds_plan(const dl_cheb_rounds_args *args, dl_mix_plan *plan) {
+    return fused_round_plan(dl::shape_cheb_rounds, args, plan);
+}
+
+int dl_cheb_rounds(const dl_cheb_rounds_args *args, void *workspace, size_t ws_bytes,
+                   dl_stream_t stream) {
+    return fused_round(dl::shape_cheb_rounds, "mix_cheb_multi_kernel", args, workspace, ws_bytes,
                        stream);
 }
 

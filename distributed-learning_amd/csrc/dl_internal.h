@@ -101,6 +101,15 @@ hipError_t launch_mix_trace(const TileArgs &a, int chunks, bool planes, int roun
 // narrow: 2-column steps (8-byte image entries) and a 6-byte LDS tail, for larger CSRs
 hipError_t launch_mix_trace_irr(const TileArgs &a, int head, bool general_mean, bool narrow,
                                 int rounds, int grid, int lds, float *trace_out, hipStream_t s);
+// the traced kernels' reduce alone (mix_trace.hip): [nparts][rounds][n_rows] partials ->
+// trace_out[rounds], summed in workgroup order
+hipError_t launch_trace_reduce(const float *partial, int nparts, int rounds, int n_rows,
+                               float *trace_out, hipStream_t s);
+// K Chebyshev rounds on LDS-resident tiles (mix_cheb_multi.hip) for the launch shape_cheb_rounds
+// shaped: mix_multi's geometry; out 0 / 1 / 2: nothing, the final deviation's partial rows, the
+// traced pass (rounds <= kChebTraceRounds) with its reduce into q.trace
+hipError_t launch_mix_cheb_multi(const TileArgs &a, const ChebMultiArgs &q, int chunks, int rounds,
+                                 int out, int grid, int lds, hipStream_t s);
 // max_zeroed: an earlier launch on the stream already zeroed dev_max (TileArgs::dev_max_zero)
 hipError_t launch_dev_reduce(const float *partial, int nparts, int n_rows, float *dev_sq,
                              float *dev_max, hipStream_t s, bool max_zeroed = false);

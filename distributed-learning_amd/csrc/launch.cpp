@@ -1078,6 +1078,135 @@ int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k
     return DL_OK;
 }
 
+int shape_cheb_rounds(const dl_cheb_rounds_args *a, int n_cus, const Knobs &k, void *ws,
+                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: args is NULL");
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_cheb_rounds_plan: plan is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y) return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: null x/y");
+    if (m.g)
+        return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: g must be NULL (no local step inside "
+                                         "the accelerated rounds)");
+    const FusedRound fr{"dl_cheb_rounds", "Chebyshev", kLaunchChebMulti, nullptr, 0};
+    int rc = whole_round(fr, m, err);
+    if (rc) return rc;
+    if (a->rounds < 1)
+        return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: rounds must be >= 1 (got %d)", a->rounds);
+    if (a->trace && a->rounds > kChebTraceRounds)
+        return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: a traced pass runs at most %d rounds "
+                                         "(got %d)", kChebTraceRounds, a->rounds);
+    const Layout lay(m);
+    const size_t yb = lay.span(m.ldy);
+    if (a->z_out && overlaps(m.y, yb, a->z_out, lay.span(a->ldzo)))
+        return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: y overlaps z_out (u_K and u_{K-1} are "
+                                         "two matrices)");
+    if ((a->z && lay.bad_ld(a->ldz)) || (a->z_out && lay.bad_ld(a->ldzo)))
+        return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: z and z_out laid out as x (row-major ld "
+                                         ">= n_params; column-tiled ld 0 or >= n_rows)");
+    if (!a->coef && (a->rounds > 1 || a->z))
+        return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: coef is NULL (read for every round but "
+                                         "a first one without z)");
+    // an output may be an input itself, never overlap it otherwise (y against x: whole_round)
+    const Span outs[2] = {{m.y, yb}, {a->z_out, a->z_out ? lay.span(a->ldzo) : 0}};
+    const int64_t out_ld[2] = {m.ldy, a->ldzo};
+    const Span ins[2] = {{m.x, lay.span(m.ldx)}, {a->z, a->z ? lay.span(a->ldz) : 0}};
+    const int64_t in_ld[2] = {m.ldx, a->ldz};
+    const char *const out_name[2] = {"y", "z_out"}, *const in_name[2] = {"x", "z"};
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) {
+            if (!outs[i].n || !ins[j].n) continue;
+            const bool same = outs[i].p == ins[j].p && out_ld[i] == in_ld[j];
+            if (!same && overlaps(outs[i].p, outs[i].n, ins[j].p, ins[j].n))
+                return fail(err, DL_ERR_INVALID, "dl_cheb_rounds: %s overlaps %s (it may be %s "
+                                                 "itself with the same ld)", out_name[i],
+                            in_name[j], in_name[j]);
+        }
+    const bool dev = m.dev_sq || m.dev_max || m.mean;
+    if ((dev || a->trace) && !m.W.doubly_stochastic)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_rounds: the deviation and the trace need a "
+                                             "doubly stochastic W (W.doubly_stochastic)");
+    Plan p1, pl;
+    rc = plan_mix(m, n_cus, k, &p1, err);
+    if (rc) return rc;
+    if (p1.pub.path != 1)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_rounds: the Chebyshev rounds run on the LDS "
+                                             "tile geometry (plan path 1); this round plans path "
+                                             "%d", p1.pub.path);
+    // the geometry of dl_mix_rounds with a deviation for the same operands: the kernel forms the
+    // column means in every call (one instantiation with and without the outputs)
+    dl_mix_args mg = m;
+    mg.mean = const_cast<float *>(m.x);   // (only its being set is read)
+    mg.W.doubly_stochastic = 1;
+    rc = plan_rounds(mg, n_cus, k, &pl, err);
+    if (rc) return rc;
+    const int32_t Nr = m.W.n_rows;
+    const int64_t scratch = (int64_t)(kTileThreads / 64) * pl.chunks * 16;
+    const int64_t lds = (int64_t)pl.pub.lds_bytes + scratch;
+    if (lds > kLdsBytes)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_rounds: two %d-column tiles of %d rows and "
+                                             "the two mean scratches do not fit LDS",
+                    4 * pl.chunks, Nr);
+    if (a->trace && tile_passes(pl.chunks, Nr, true) > kChebTraceMaxKv)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_rounds: a traced pass holds at most %d rows "
+                                             "per thread (%d agents at %d columns)",
+                    kChebTraceMaxKv, kChebTraceMaxKv * kTileThreads / pl.chunks, 4 * pl.chunks);
+    pl.pub.lds_bytes = (int32_t)lds;
+    if (plan) *plan = pl.pub;
+    if (!out) return DL_OK;
+
+    reset(out);
+    Launch &l = out->l[0];
+    l.t = tile_args(m, k);
+    TileArgs &t = l.t;
+    if (!t.vec || (a->z && !lay.reach(a->z, a->ldz)) ||
+        (a->z_out && !lay.reach(a->z_out, a->ldzo)))
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_cheb_rounds: operands must be 16-byte aligned "
+                                             "float4 rows");
+    set_tile_strides(t, pl.pub.tile_cols);
+    t.n_tiles = pl.pub.n_tiles;
+    t.col_base = 0;
+    t.csr_off = pl.csr_off;
+    t.scratch_off = pl.scratch_off;
+    l.kind = kLaunchChebMulti;
+    l.chunks = pl.chunks;
+    l.rounds = a->rounds;
+    l.grid = pl.pub.grid;
+    l.lds = (int32_t)lds;
+    l.fast = true;
+    l.dev = dev;
+    l.out = a->trace ? 2 : dev ? 1 : 0;
+    ChebMultiArgs &q = l.m;
+    q.plain0 = a->z ? 0 : 1;
+    q.z = a->z ? a->z : m.x;
+    q.ldz = a->z ? a->ldz : m.ldx;
+    q.z_out = a->z_out;
+    q.ldzo = a->ldzo;
+    extra_stride(l, q.ldz, &q.zts, &q.zrs);
+    extra_stride(l, q.ldzo, &q.zots, &q.zors);
+    q.coef = a->coef;
+    q.scratch2_off = (uint32_t)(pl.scratch_off + scratch);
+    q.trace = a->trace;
+    const size_t trace_b = cheb_rounds_workspace_bytes(l.grid, Nr, a->rounds, a->trace, false);
+    const size_t need = cheb_rounds_workspace_bytes(l.grid, Nr, a->rounds, a->trace, dev);
+    if (need && !ws_holds(ws, ws_bytes, need))
+        return fail(err, DL_ERR_WORKSPACE, "dl_cheb_rounds: needs a 16-byte aligned workspace of "
+                                           "%zu bytes (dl_cheb_rounds_workspace_bytes)", need);
+    float *final_rows = dev ? reinterpret_cast<float *>(static_cast<char *>(ws) + trace_b) : nullptr;
+    if (a->trace) {
+        t.dev_partial = static_cast<float *>(ws);
+        q.dev_final = final_rows;
+    } else {
+        t.dev_partial = final_rows;
+    }
+    if (dev) t.dev_max_zero = reinterpret_cast<unsigned int *>(m.dev_max);
+    out->n = 1;
+    if (dev) {
+        if (Nr <= 1) out->after = kAfterZero;
+        else after_reduce(out, final_rows, l.grid, Nr, true);
+    }
+    return DL_OK;
+}
+
 int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                 size_t ws_bytes, Launches *out, char *err) {
     reset(out);

@@ -3,8 +3,8 @@
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
 // rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round,
-// dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist, dl_dense_round, dl_band_round and
-// their plan queries),
+// dl_cheb_rounds, dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist, dl_dense_round,
+// dl_band_round and their plan queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -129,6 +129,25 @@ struct ChebTileArgs {
     int64_t zts;    // FAST-path tile stride in bytes
     uint32_t zrs;   // FAST-path row stride in bytes
     float a, b;
+};
+
+// The multi-round Chebyshev pass's operands beside x and y (mix_cheb_multi.hip): z = u_{-1} and
+// z_out = u_{K-1} (nullable), each laid out as x, with their FAST-path strides (tile_stride); the
+// device table of coefficient pairs; the second mean scratch in LDS; the outputs of the traced
+// pass.  plain0: the call had no z -- round 0 is the plain fold, coef[0..1] is not read, and z is
+// x itself (loaded, never used) so the kernel's loads do not depend on it.
+struct ChebMultiArgs {
+    const float *z;
+    int64_t ldz;
+    float *z_out;
+    int64_t ldzo;
+    int64_t zts, zots;    // FAST-path tile strides in bytes
+    uint32_t zrs, zors;   // FAST-path row strides in bytes
+    const float *coef;    // [2 x rounds]: a_r, b_r
+    int32_t plain0;
+    uint32_t scratch2_off;   // byte offset of the 16 x C float4 scratch of z's column sums
+    float *dev_final;     // traced pass with deviation outputs: [grid][n_rows] partial rows
+    float *trace;         // traced pass: [rounds]
 };
 
 // The gradient-tracking round's operands beside x, g and y (mix_track.hip): the tracker d, its
@@ -331,6 +350,7 @@ enum LaunchKind : int32_t {
     kLaunchAdamTile,  // launch_mix_adam_tile(t, a, chunks, dev, grid, lds, fast)
     kLaunchTrimTile,  // launch_mix_trim_tile(t, r, chunks, dev, grid, lds, fast)
     kLaunchEdgeTile,  // launch_mix_edge_tile(t, e, chunks, grid, lds, fast)
+    kLaunchChebMulti, // launch_mix_cheb_multi(t, m, chunks, rounds, out, grid, lds): + its reduce
 };
 struct Launch {
     int32_t kind;
@@ -346,6 +366,8 @@ struct Launch {
     AdamTileArgs a;            // kLaunchAdamTile
     TrimTileArgs r;            // kLaunchTrimTile
     EdgeTileArgs e;            // kLaunchEdgeTile
+    ChebMultiArgs m;           // kLaunchChebMulti
+    int32_t out;               // kLaunchChebMulti: 0 nothing, 1 final deviation, 2 traced
 };
 // What follows the launches on the stream.
 enum After : int32_t {
@@ -418,6 +440,21 @@ int shape_rounds(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k
                  size_t ws_bytes, Launches *out, char *err);
 int shape_trace(const dl_mix_args &a, int32_t rounds, int n_cus, const Knobs &k, void *ws,
                 size_t ws_bytes, Launches *out, char *err);
+// dl_cheb_rounds / dl_cheb_rounds_plan: K Chebyshev rounds on LDS-resident tiles.  The checks in
+// the header's order, each refusal with its own text; the round must plan path 1 (plan_mix) and
+// then takes plan_rounds' geometry for the same dl_mix_args with a deviation -- the tile width at
+// which two images fit -- plus a second mean scratch behind it, in every call: the kernel forms
+// the column means whether or not an output is asked for.
+// Workspace (cheb_rounds_workspace_bytes): the traced pass's [grid][rounds][n_rows] partial rows,
+// then the final deviation's [grid][n_rows].  out NULL: the plan query, which needs `plan`
+// (path 3, as dl_mix_rounds_plan reports it).
+int shape_cheb_rounds(const dl_cheb_rounds_args *a, int n_cus, const Knobs &k, void *ws,
+                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
+constexpr size_t cheb_rounds_workspace_bytes(int64_t grid, int32_t n_rows, int32_t rounds,
+                                             bool trace, bool dev) {
+    return (trace ? partial_bytes(grid * rounds, n_rows) : 0) +
+           (dev ? partial_bytes(grid, n_rows) : 0);
+}
 // One-pass deviation of x on the tile kernel (MIX = false): every agent of a column tile in one
 // workgroup, column mean in LDS scratch.  tile_cols > 0: x in the column-tiled layout (ldx 0).
 // DL_ERR_UNSUPPORTED without a text: the agents do not fit one tile.

@@ -959,12 +959,17 @@ hipError_t launch_irr1(const TileArgs &a, int head, bool narrow, int rounds, int
 // the traced kernel's [grid][rounds][n_rows] partials -> trace_out[rounds]
 hipError_t launch_trace_reduce(const TileArgs &a, int rounds, int grid, float *trace_out,
                                hipStream_t s) {
-    hipLaunchKernelGGL(trace_reduce_kernel, dim3(rounds), dim3(1024), 0, s, a.dev_partial, grid,
-                       rounds, a.n_rows, trace_out);
-    return hipGetLastError();
+    return dl::launch_trace_reduce(a.dev_partial, grid, rounds, a.n_rows, trace_out, s);
 }
 
 }  // namespace
+
+hipError_t launch_trace_reduce(const float *partial, int nparts, int rounds, int n_rows,
+                               float *trace_out, hipStream_t s) {
+    hipLaunchKernelGGL(trace_reduce_kernel, dim3(rounds), dim3(1024), 0, s, partial, nparts,
+                       rounds, n_rows, trace_out);
+    return hipGetLastError();
+}
 
 hipError_t launch_mix_trace_irr(const TileArgs &a, int head, bool general_mean, bool narrow,
                                 int rounds, int grid, int lds, float *trace_out, hipStream_t s) {

@@ -176,5 +176,9 @@ constexpr int irr_trace_kv(int n_rows) {
     return n_rows <= kTileThreads ? 1 : n_rows <= 2 * kTileThreads ? 2 : 4;
 }
 constexpr int irr_trace_rounds(int kv) { return kv == 1 ? 24 : kv == 2 ? 12 : 4; }
+// dl_cheb_rounds' traced pass (mix_cheb_multi.hip: mix_multi_kernel's geometry, up to
+// kChebTraceMaxKv rows per thread x kChebTraceRounds per-round sums in VGPRs)
+constexpr int kChebTraceRounds = 8;
+constexpr int kChebTraceMaxKv = 4;
 
 }  // namespace dl

@@ -404,6 +404,59 @@ def cheb_round(W: DeviceCsr, X, Y, Z, a, b, dev_sq=None, dev_max=None, mean=None
     return _fused_round_run("dl_cheb_round", args, W, P, workspace)
 
 
+CHEB_TRACE_ROUNDS = 8   # rounds of one traced cheb_rounds pass (csrc/plan.h kChebTraceRounds)
+
+
+def _cheb_rounds_args(W, X, Y, Z, Zout, coef, rounds, trace, dev_sq, dev_max, mean, tiled):
+    mix, (ldz, ldzo) = _fused_round_operands("cheb_rounds", None, W, X, Y, None, 0.0, dev_sq,
+                                             dev_max, mean, tiled, (("Z", Z), ("Zout", Zout)))
+    rounds = int(rounds)
+    for name, t, n in (("coef", coef, 2 * rounds), ("trace", trace, rounds)):
+        if t is not None and (t.dtype != torch.float32 or t.device != W.device or
+                              not t.is_contiguous() or t.numel() < n):
+            raise ValueError(f"{name} must be a contiguous float32 device tensor of at least "
+                             f"{n} entries")
+    return _lib.DlChebRoundsArgs(mix, _lib.ptr(Z), ldz, _lib.ptr(Zout), ldzo, _lib.ptr(coef),
+                                 rounds, _lib.ptr(trace))
+
+
+def cheb_rounds_plan(W: DeviceCsr, X, Y, Z=None, Zout=None, deviation=False, traced=False,
+                     tiled=None):
+    """dl_cheb_rounds_plan: the configuration ``cheb_rounds`` would run for these operands (with
+    a trace: ``traced``), or None when the multi-round Chebyshev kernel does not take them."""
+    coef = torch.zeros(2, dtype=torch.float32, device=W.device)
+    return _fused_round_plan(
+        "dl_cheb_rounds_plan",
+        lambda dev_sq, dev_max: _cheb_rounds_args(W, X, Y, Z, Zout, coef, 1,
+                                                  coef if traced else None, dev_sq, dev_max,
+                                                  None, tiled),
+        W, deviation)
+
+
+def cheb_rounds(W: DeviceCsr, X, Y, Z, Zout, coef, rounds, trace=None, dev_sq=None, dev_max=None,
+                mean=None, workspace: Workspace = None, tiled=None):
+    """``rounds`` = K rounds of Chebyshev-accelerated gossip in one HBM pass on the current stream
+    (dl_cheb_rounds): with u_0 = X, u_-1 = Z, round r is u_r+1 = fl(fl(a_r (W u_r)) + fl(b_r
+    u_r-1)) with (a_r, b_r) = coef[2r], coef[2r + 1] (a float32 DEVICE tensor); Y = u_K and Zout
+    (optional) = u_K-1 -- bit for bit ``mix_round`` / ``cheb_round`` called K times.  Z None:
+    round 0 is the plain round (coef[0:2] not read).  Y and Zout may each be X or Z themselves.
+    trace (optional, float32 device [K], K <= CHEB_TRACE_ROUNDS): the max deviation after every
+    round.  ``tiled=(n_params, tile_cols)``: every operand in the column-tiled layout.  Returns
+    False, launching nothing, when the kernel does not take the shape (the caller then loops
+    ``mix_round`` / ``cheb_round``)."""
+    lib = _lib.load()
+    P = tiled[0] if tiled is not None else X.shape[1]
+    args = _cheb_rounds_args(W, X, Y, Z, Zout, coef, rounds, trace, dev_sq, dev_max, mean, tiled)
+    workspace = workspace or Workspace(W.device)
+    wp, wn = workspace.ptr_size(lib.dl_cheb_rounds_workspace_bytes(
+        W.n_rows, int(rounds), int(trace is not None)))
+    rc = lib.dl_cheb_rounds(ctypes.byref(args), wp, wn, _lib.stream_handle(W.device))
+    if rc == _lib.DL_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc, "dl_cheb_rounds")
+    return True
+
+
 def _track_round_args(W, X, Y, D, Dout, G, Gold, lr, dev_sq, dev_max, mean, tiled):
     missing = ("track_round needs the tracker D, its output Dout and the gradients G, Gold"
                if D is None or Dout is None or G is None or Gold is None else None)
@@ -1613,7 +1666,76 @@ class GossipEngine:
         adam_step(flat(self.X), flat(G), flat(self.M), flat(self.V), out=flat(self._S), **opt)
         self.round(src=self._S, deviation=deviation, mean=mean)
 
-    def mix_chebyshev(self, gamma, times=1, eps=None, on_deviation=None):
+    def _mix_chebyshev_passes(self, gamma, rounds, times, eps, on_deviation):
+        """``mix_chebyshev`` in ``cheb_rounds`` passes: (rounds done, finished).  Not finished --
+        after 0 rounds where the kernel does not take this engine's shape -- leaves X, Y the
+        iterates after ``done`` rounds and the one before, for the per-round loop to go on."""
+        from .utils.fast_averaging import chebyshev_omegas
+        tiled = (self.P, self.T) if self.layout == "tiled" else None
+
+        def table(n):   # (w_k, 1 - w_k) formed in double, rounded as the per-round loop does
+            om = chebyshev_omegas(gamma, n)
+            pairs = np.array([[np.float32(w), np.float32(1.0 - w)] for w in om], np.float32)
+            return torch.from_numpy(pairs.reshape(-1)).to(self.device)
+
+        coef = table(max(rounds, 64))
+
+        def run(k, done, Y, Zout, trace=None, dev=False):
+            return cheb_rounds(self.W, self.X, Y, self.Y if done else None, Zout,
+                               coef[2 * done:], k, trace=trace,
+                               dev_sq=self.dev_sq if dev else None,
+                               dev_max=self.dev_max if dev else None, workspace=self.ws,
+                               tiled=tiled)
+
+        done = 0
+        if eps is None:
+            # in place: u_K over the older iterate, u_{K-1} over x
+            while done < rounds:
+                k = min(64, rounds - done)
+                if not run(k, done, self.Y, self.X):
+                    return done, False
+                self.X, self.Y = self.Y, self.X
+                done += k
+            return done, True
+        # traced passes run out of place: a stop inside a pass re-runs that many rounds from
+        # the pass's inputs
+        KT = CHEB_TRACE_ROUNDS
+        if cheb_rounds_plan(self.W, self.X, self.Y, deviation=True, traced=True,
+                            tiled=tiled) is None:
+            return 0, False
+        if getattr(self, "_cheb_out", None) is None:
+            self._cheb_out = (self._empty(), self._empty())
+            self._cheb_trace = torch.zeros(KT, dtype=torch.float32, device=self.device)
+        while True:
+            if 2 * (done + KT) > coef.numel():
+                coef = table(coef.numel())
+            A, B = self._cheb_out
+            if not run(KT, done, A, B, trace=self._cheb_trace, dev=True):
+                return done, False
+            trace = self._cheb_trace.cpu().numpy()
+            stop, stopped, nan = KT, False, None
+            for j in range(1, KT + 1):
+                max_dev = np.float32(trace[j - 1])
+                if on_deviation is not None:
+                    on_deviation(max_dev)
+                try:
+                    if below_eps(max_dev, eps, done + j) and done + j >= times:
+                        stop, stopped = j, True
+                        break
+                except FloatingPointError as e:
+                    stop, nan = j, e
+                    break
+            if stop < KT:
+                run(stop, done, A, B, dev=True)
+            self._cheb_out = (self.X, self.Y)
+            self.X, self.Y = A, B
+            done += stop
+            if nan is not None:
+                raise nan
+            if stopped:
+                return done, True
+
+    def mix_chebyshev(self, gamma, times=1, eps=None, on_deviation=None, passes=None):
         """``Mixer.mix``'s loop with the rounds accelerated by the Chebyshev semi-iteration
         (``utils.fast_averaging.chebyshev_omegas``): round 1 is the plain ``round()`` -- its bits
         are the reference's -- and round k >= 2 is ``round_cheb(float32(w_k), float32(1 - w_k))``,
@@ -1629,7 +1751,16 @@ class GossipEngine:
         ``spectral_gamma`` return); W must be symmetric.  The per-round contraction becomes
         gamma / (1 + sqrt(1 - gamma^2)) instead of gamma.  A gamma below the true one can
         diverge; a gamma above it only converges more slowly.  The deviation sequence is not
-        monotone."""
+        monotone.
+
+        ``passes`` (None or True: on; False: the per-round loop): the rounds run in
+        ``cheb_rounds`` passes on LDS-resident tiles, up to 64 rounds a pass with ``eps=None``;
+        with an eps, traced passes of CHEB_TRACE_ROUNDS rounds with one readback of the trace
+        per pass, the stop rule applied to every traced round in order, and a stop inside a pass
+        re-run from the pass's inputs (two more resident matrices, allocated once the kernel is
+        known to take the shape).  Rounds done and the final iterate are bit for bit the
+        per-round loop's.  Where the kernel does not take the engine's shape the per-round loop
+        runs.  Measured: profiles/r30/cheb_rounds."""
         import math
         from .utils.fast_averaging import chebyshev_omegas
         gamma = float(gamma)
@@ -1640,8 +1771,13 @@ class GossipEngine:
         rounds = math.ceil(times)
         if eps is None and rounds < 1:
             return 0
-        omegas = chebyshev_omegas(gamma, max(rounds, 64))
-        done = 0
+        if passes or passes is None:
+            done, finished = self._mix_chebyshev_passes(gamma, rounds, times, eps, on_deviation)
+            if finished:
+                return done
+        else:
+            done = 0
+        omegas = chebyshev_omegas(gamma, max(rounds, done + 1, 64))
         while True:
             if done == 0:
                 self.round(deviation=eps is not None)

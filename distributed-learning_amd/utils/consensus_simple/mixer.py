@@ -138,7 +138,7 @@ class Mixer(object):
         self.logger.debug('Mixer finished with {} times'.format(times_done))
         return times_done
 
-    def mix_chebyshev(self, gamma, times=1, eps=None):
+    def mix_chebyshev(self, gamma, times=1, eps=None, passes=None):
         """``mix`` with the rounds accelerated by the Chebyshev semi-iteration
         (``GossipEngine.mix_chebyshev``): the same flattening, stop rule, log lines, write-back
         and return value, a fraction of the rounds.  ``gamma`` is the spectral radius of W -
@@ -146,7 +146,10 @@ class Mixer(object):
         weights the topology was built from, or ``spectral_gamma(graph, weights)`` for any
         others; the topology must be symmetric.  A gamma below the true one can diverge; one
         above it only converges more slowly.  The deviation tested against ``eps`` is the default
-        metric's (fused into the round); a custom ``dev_metric`` with ``eps`` is refused."""
+        metric's (fused into the round); a custom ``dev_metric`` with ``eps`` is refused.
+        ``passes``: as ``GossipEngine.mix_chebyshev``'s (None or True: the rounds in multi-round
+        passes on LDS-resident tiles where the kernel takes the layout; False: the per-round
+        loop)."""
         if len(self.topology) <= 1:
             return 0
         if eps is not None and self._custom_metric:
@@ -165,7 +168,8 @@ class Mixer(object):
 
             def log(max_dev):
                 self.logger.debug('Mixer calculate max deviation= {}'.format(max_dev))
-            times_done = eng.mix_chebyshev(gamma, times, eps, on_deviation=log)
+            times_done = eng.mix_chebyshev(gamma, times, eps, on_deviation=log,
+                                           passes=passes)
             self._write_back(eng.rows())
 
         self.logger.debug('Mixer finished with {} times'.format(times_done))

@@ -530,6 +530,54 @@ typedef struct dl_cheb_round_args {
 int dl_cheb_round_plan(const dl_cheb_round_args *args, dl_mix_plan *plan);
 int dl_cheb_round(const dl_cheb_round_args *args, void *workspace, size_t ws_bytes,
                   dl_stream_t stream);
+/* `rounds` = K >= 1 rounds of the same recurrence in ONE pass over HBM, on LDS-resident column
+ * tiles (dl_mix_rounds' geometry: two tile images of all agents): with u_0 = x, u_{-1} = z,
+ *   u_{r+1}[row] = fl(fl(a_r fold_W(u_r)[row]) + fl(b_r u_{r-1}[row])),   r = 0 .. K-1,
+ * fold_W the left fold of dl_mix_round (from +0.0 in CSR order, product and sum separate fp32
+ * operations) and the combine dl_axpby's three roundings; (a_r, b_r) = coef[2r], coef[2r + 1], a
+ * DEVICE table of 2K floats.  With z NULL round 0 is the plain fold alone -- dl_mix_round's bits,
+ * coef[0..1] not read -- which is how the semi-iteration starts.  y = u_K; z_out (nullable) =
+ * u_{K-1}, for K = 1 a copy of x.  K rounds here are bit for bit dl_mix_round / dl_cheb_round
+ * called K times, and so is any split of K into consecutive passes (y, z_out of one the x, z of
+ * the next).  HBM sees 16 B per element per pass (x, z in; y, z_out out) whatever K is.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   Aliasing: y and z_out may each be x or z themselves (same ld), in either assignment -- y = x
+ *     with z_out = z, or y = z with z_out = x (a workgroup stages all rows of its columns before
+ *     it writes any) -- or overlap nothing.  y and z_out must not overlap each other.
+ *   z and z_out are laid out as x (dl_cheb_round's rule for ldz); operands 16-byte aligned, and
+ *     row-major n_params a multiple of the tile width, as dl_mix_rounds asks.
+ *   dev_sq / dev_max / mean describe u_K; trace (nullable, device float[K], K <= 8 rounds a pass,
+ *     at most 4096 x 4 / tile_cols agents) receives max_a ||u_{r+1,a} - m_{r+1}||_2 for every
+ *     round.  Both need W.doubly_stochastic = 1 (the semi-iteration needs a symmetric W anyway).
+ *     The mean is DEFINED by the recurrence: m_0, m_{-1} the column means of x and z (fp32 sums of
+ *     the staged tile in a fixed order, divided by n_rows), m_{r+1} = fl(fl(a_r m_r) + fl(b_r
+ *     m_{r-1})) (m_1 = m_0 with z NULL) -- exact for a doubly stochastic W in real arithmetic.
+ *     Sums in a fixed order: the bits repeat from run to run.
+ *   DL_ERR_INVALID: args NULL, x or y NULL; mix.g != NULL ("g must be NULL"); what dl_mix_round
+ *     refuses; rounds < 1; trace with rounds > 8; y overlapping z_out; z or z_out not laid out as
+ *     x; coef NULL when it would be read (rounds > 1 or z given); an overlap of an output with x
+ *     or z other than being it; dl_cheb_rounds_plan with plan NULL.
+ *   DL_ERR_UNSUPPORTED (the caller loops dl_mix_round / dl_cheb_round): any halo, partition or
+ *     lagged-deviation field; a round that plans path 2, 4 or 5; operands the float4 kernels do
+ *     not reach; a deviation or trace without the doubly stochastic promise; two tile images (and
+ *     the mean scratches) that do not fit LDS; a trace at more than 4 rows per thread.
+ *   DL_ERR_WORKSPACE: less than dl_cheb_rounds_workspace_bytes(n_rows, rounds, trace != NULL).
+ *   Stream-ordered, no host synchronisation, no allocation.
+ * dl_cheb_rounds_plan: DL_OK and the configuration (path 3, as dl_mix_rounds_plan), or the
+ * refusal, without touching the device. */
+typedef struct dl_cheb_rounds_args {
+    dl_mix_args mix;   /* x, y, W, n_params, ld*, tile_cols, dev_sq, dev_max, mean; the rest as
+                          dl_cheb_round_args */
+    const float *z; int64_t ldz;      /* nullable: u_{-1}, laid out as x */
+    float *z_out; int64_t ldzo;       /* nullable: u_{K-1}, laid out as x */
+    const float *coef;                /* device float[2 * rounds] */
+    int32_t rounds;
+    float *trace;                     /* nullable: device float[rounds] */
+} dl_cheb_rounds_args;
+size_t dl_cheb_rounds_workspace_bytes(int32_t n_rows, int32_t rounds, int32_t trace);
+int dl_cheb_rounds_plan(const dl_cheb_rounds_args *args, dl_mix_plan *plan);
+int dl_cheb_rounds(const dl_cheb_rounds_args *args, void *workspace, size_t ws_bytes,
+                   dl_stream_t stream);
 /* One gradient-tracking round in one HBM pass (no reference counterpart: the reference's loops run
  * decentralized gradient descent, X <- W (X - lr G), which with a constant step stalls at a bias
  * proportional to lr x the heterogeneity of the agents' gradients).  Each agent carries a tracker
