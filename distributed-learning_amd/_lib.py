@@ -110,6 +110,12 @@ class DlChebRoundsArgs(ctypes.Structure):
                 ("coef", _vp), ("rounds", _i32), ("trace", _vp)]
 
 
+class DlDropRoundsArgs(ctypes.Structure):
+    _fields_ = [("mix", DlMixArgs), ("rounds", _i32), ("seed", ctypes.c_uint32),
+                ("round0", ctypes.c_uint32), ("round0_dev", _vp), ("thr_edge", ctypes.c_uint32),
+                ("thr_node", ctypes.c_uint32)]
+
+
 class DlTrackRoundArgs(ctypes.Structure):
     _fields_ = [("mix", DlMixArgs), ("d", _vp), ("ldd", _i64), ("d_out", _vp), ("lddo", _i64),
                 ("g_old", _vp), ("ldq", _i64)]
@@ -269,6 +275,10 @@ SIGNATURES = {
     "dl_cheb_rounds_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dl_cheb_rounds_plan": (_i32, [ctypes.POINTER(DlChebRoundsArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_cheb_rounds": (_i32, [ctypes.POINTER(DlChebRoundsArgs), _vp, _sz, _vp]),
+    "dl_drop_rounds_plan": (_i32, [ctypes.POINTER(DlDropRoundsArgs), ctypes.POINTER(DlMixPlan)]),
+    "dl_drop_rounds": (_i32, [ctypes.POINTER(DlDropRoundsArgs), _vp, _sz, _vp]),
+    "dl_link_mask": (_i32, [_vp, _vp, _i32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                            ctypes.c_uint32, _vp]),
     "dl_track_round_plan": (_i32, [ctypes.POINTER(DlTrackRoundArgs), ctypes.POINTER(DlMixPlan)]),
     "dl_track_round": (_i32, [ctypes.POINTER(DlTrackRoundArgs), _vp, _sz, _vp]),
     "dl_adam_tick": (_i32, [_vp, _vp]),

@@ -170,6 +170,10 @@ int run(const dl::Launches &L, float *dev_sq, float *dev_max, float *trace, cons
                 e = dl::launch_mix_cheb_multi(l.t, l.m, l.chunks, l.rounds, l.out, l.grid, l.lds, s);
                 who = "mix_cheb_multi_kernel launch";
                 break;
+            case dl::kLaunchDrop:
+                e = dl::launch_mix_drop(l.t, l.d, l.chunks, l.sgd, l.grid, l.lds, s);
+                who = "mix_drop_kernel launch";
+                break;
             case dl::kLaunchTrace:
                 e = dl::launch_mix_trace(l.t, l.chunks, l.planes, l.rounds, l.grid, l.lds, trace,
                                          s);
@@ -749,6 +753,24 @@ int dl_cheb_rounds(const dl_cheb_rounds_args *args, void *workspace, size_t ws_b
                    dl_stream_t stream) {
     return fused_round(dl::shape_cheb_rounds, "mix_cheb_multi_kernel", args, workspace, ws_bytes,
                        stream);
+}
+
+int dl_drop_rounds_plan(const dl_drop_rounds_args *args, dl_mix_plan *plan) {
+    return fused_round_plan(dl::shape_drop_rounds, args, plan);
+}
+
+int dl_drop_rounds(const dl_drop_rounds_args *args, void *workspace, size_t ws_bytes,
+                   dl_stream_t stream) {
+    return fused_round(dl::shape_drop_rounds, "mix_drop_kernel", args, workspace, ws_bytes,
+                       stream);
+}
+
+int dl_link_mask(const int32_t *row_ptr, const int32_t *col, int32_t n_rows, uint32_t seed,
+                 uint32_t round, uint32_t thr_edge, uint32_t thr_node, uint8_t *up) {
+    g_err.clear();
+    char err[dl::kErrLen];
+    return status(dl::link_mask(row_ptr, col, n_rows, seed, round, thr_edge, thr_node, up, err),
+                  err);
 }
 
 int dl_track_round_plan(const dl_track_round_args *args, dl_mix_plan *plan) {

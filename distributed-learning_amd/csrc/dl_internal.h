@@ -110,6 +110,10 @@ hipError_t launch_trace_reduce(const float *partial, int nparts, int rounds, int
 // traced pass (rounds <= kChebTraceRounds) with its reduce into q.trace
 hipError_t launch_mix_cheb_multi(const TileArgs &a, const ChebMultiArgs &q, int chunks, int rounds,
                                  int out, int grid, int lds, hipStream_t s);
+// K rounds over failing links on LDS-resident tiles (mix_drop.hip) for the launch
+// shape_drop_rounds shaped: mix_multi's geometry, the deviation's partial rows when a.dev_partial
+hipError_t launch_mix_drop(const TileArgs &a, const DropArgs &q, int chunks, bool sgd, int grid,
+                           int lds, hipStream_t s);
 // max_zeroed: an earlier launch on the stream already zeroed dev_max (TileArgs::dev_max_zero)
 hipError_t launch_dev_reduce(const float *partial, int nparts, int n_rows, float *dev_sq,
                              float *dev_max, hipStream_t s, bool max_zeroed = false);

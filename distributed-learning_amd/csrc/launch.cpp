@@ -4,6 +4,8 @@
 
 #include <cstring>
 
+#include "link_hash.h"
+
 namespace dl {
 
 void tile_stride(bool tiled, int64_t ld, int64_t rows, int64_t T, int64_t *ts, uint32_t *rs) {
@@ -1203,6 +1205,91 @@ int shape_cheb_rounds(const dl_cheb_rounds_args *a, int n_cus, const Knobs &k, v
     if (dev) {
         if (Nr <= 1) out->after = kAfterZero;
         else after_reduce(out, final_rows, l.grid, Nr, true);
+    }
+    return DL_OK;
+}
+
+int shape_drop_rounds(const dl_drop_rounds_args *a, int n_cus, const Knobs &k, void *ws,
+                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err) {
+    if (!a) return fail(err, DL_ERR_INVALID, "dl_drop_rounds: args is NULL");
+    if (!out && !plan) return fail(err, DL_ERR_INVALID, "dl_drop_rounds_plan: plan is NULL");
+    const dl_mix_args &m = a->mix;
+    if (!m.x || !m.y) return fail(err, DL_ERR_INVALID, "dl_drop_rounds: null x/y");
+    const FusedRound fr{"dl_drop_rounds", "failing-link", kLaunchDrop, nullptr, 0};
+    int rc = whole_round(fr, m, err);
+    if (rc) return rc;
+    if (a->rounds < 1)
+        return fail(err, DL_ERR_INVALID, "dl_drop_rounds: rounds must be >= 1 (got %d)", a->rounds);
+    const bool dev = m.dev_sq || m.dev_max || m.mean;
+    if (dev && !m.W.doubly_stochastic)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_drop_rounds: the deviation needs a doubly "
+                                             "stochastic W (W.doubly_stochastic)");
+    Plan p1, pl;
+    rc = plan_mix(m, n_cus, k, &p1, err);
+    if (rc) return rc;
+    if (p1.pub.path != 1)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_drop_rounds: the failing-link rounds run on the "
+                                             "LDS tile geometry (plan path 1); this round plans "
+                                             "path %d", p1.pub.path);
+    char why[kErrLen];
+    rc = plan_rounds(m, n_cus, k, &pl, why);
+    if (rc)   // (the halo and deviation refusals of plan_rounds were given above)
+        return fail(err, rc, "dl_drop_rounds: two tile images of %d rows do not fit LDS at a tile "
+                             "width these operands allow (%.300s)", m.W.n_rows, why);
+    if (plan) *plan = pl.pub;
+    if (!out) return DL_OK;
+
+    reset(out);
+    const int32_t Nr = m.W.n_rows;
+    Launch &l = out->l[0];
+    l.t = tile_args(m, k);
+    TileArgs &t = l.t;
+    if (!t.vec)
+        return fail(err, DL_ERR_UNSUPPORTED, "dl_drop_rounds: operands must be 16-byte aligned "
+                                             "float4 rows");
+    set_tile_strides(t, pl.pub.tile_cols);
+    t.n_tiles = pl.pub.n_tiles;
+    t.col_base = 0;
+    t.csr_off = pl.csr_off;
+    t.scratch_off = pl.scratch_off;
+    if (dev) {
+        const size_t need = partial_bytes(pl.pub.grid, Nr);
+        if (!ws_holds(ws, ws_bytes, need))
+            return fail(err, DL_ERR_WORKSPACE, "dl_drop_rounds: deviation outputs need a 16-byte "
+                                               "aligned workspace of %zu bytes", need);
+        t.dev_partial = static_cast<float *>(ws);
+        t.dev_max_zero = reinterpret_cast<unsigned int *>(m.dev_max);
+    }
+    l.kind = kLaunchDrop;
+    l.chunks = pl.chunks;
+    l.rounds = a->rounds;
+    l.sgd = m.g != nullptr;
+    l.dev = dev;
+    l.grid = pl.pub.grid;
+    l.lds = pl.pub.lds_bytes;
+    l.fast = true;
+    l.d = DropArgs{a->rounds, a->seed, a->round0, a->round0_dev, a->thr_edge, a->thr_node};
+    out->n = 1;
+    if (dev) {
+        if (Nr <= 1) out->after = kAfterZero;
+        else after_reduce(out, t.dev_partial, pl.pub.grid, Nr, true);
+    }
+    return DL_OK;
+}
+
+int link_mask(const int32_t *rowptr, const int32_t *col, int32_t n_rows, uint32_t seed,
+              uint32_t round, uint32_t thr_edge, uint32_t thr_node, uint8_t *up, char *err) {
+    if (!rowptr || !col || !up) return fail(err, DL_ERR_INVALID, "dl_link_mask: null row_ptr/col/up");
+    if (n_rows <= 0) return fail(err, DL_ERR_INVALID, "dl_link_mask: n_rows must be > 0");
+    const uint32_t key = link_round_key(seed, round);
+    for (int32_t i = 0; i < n_rows; ++i) {
+        if (rowptr[i] < 0 || rowptr[i + 1] < rowptr[i])
+            return fail(err, DL_ERR_INVALID, "dl_link_mask: row_ptr decreases at row %d", i);
+        for (int32_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+            if (col[e] < 0) return fail(err, DL_ERR_INVALID, "dl_link_mask: col[%d] < 0", e);
+            up[e] = e == rowptr[i] ||
+                    !link_down(key, (uint32_t)i, (uint32_t)col[e], thr_edge, thr_node);
+        }
     }
     return DL_OK;
 }

@@ -3,8 +3,8 @@
 // launches -- every kernel's parameter, grid, LDS bytes and selectors, and the step after the
 // launches; the C ABI (capi.hip) turns the description into launch_* calls.  Shaped here: the
 // rounds (dl_mix_round, dl_mix_rounds, dl_mix_rounds_trace, dl_sgd_round, dl_cheb_round,
-// dl_cheb_rounds, dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist, dl_dense_round,
-// dl_band_round and their plan queries),
+// dl_cheb_rounds, dl_drop_rounds, dl_track_round, dl_adam_round, dl_trim_round, dl_edge_sqdist,
+// dl_dense_round, dl_band_round and their plan queries),
 // the one-pass deviation, dl_mlp_grad, dl_mlp_eval, dl_bgemm, dl_batch_gather, dl_image_batch,
 // dl_lenet_grad and dl_lenet_eval.  Not shaped here (capi.hip checks them itself, their LDS-size
 // functions live in kernel files): dl_mix_until, dl_consensus_gd, dl_perron_round, the two-pass
@@ -148,6 +148,15 @@ struct ChebMultiArgs {
     uint32_t scratch2_off;   // byte offset of the 16 x C float4 scratch of z's column sums
     float *dev_final;     // traced pass with deviation outputs: [grid][n_rows] partial rows
     float *trace;         // traced pass: [rounds]
+};
+
+// The failing-link pass's parameters beside the round's (mix_drop.hip; link_hash.h has the rule):
+// rounds t0 .. t0 + rounds - 1, t0 = *round0_dev when given (read, never written) else round0.
+struct DropArgs {
+    int32_t rounds;
+    uint32_t seed, round0;
+    const uint32_t *round0_dev;
+    uint32_t thr_edge, thr_node;   // a draw below it: down (0: never)
 };
 
 // The gradient-tracking round's operands beside x, g and y (mix_track.hip): the tracker d, its
@@ -351,6 +360,7 @@ enum LaunchKind : int32_t {
     kLaunchTrimTile,  // launch_mix_trim_tile(t, r, chunks, dev, grid, lds, fast)
     kLaunchEdgeTile,  // launch_mix_edge_tile(t, e, chunks, grid, lds, fast)
     kLaunchChebMulti, // launch_mix_cheb_multi(t, m, chunks, rounds, out, grid, lds): + its reduce
+    kLaunchDrop,      // launch_mix_drop(t, d, chunks, sgd, grid, lds)
 };
 struct Launch {
     int32_t kind;
@@ -368,6 +378,7 @@ struct Launch {
     EdgeTileArgs e;            // kLaunchEdgeTile
     ChebMultiArgs m;           // kLaunchChebMulti
     int32_t out;               // kLaunchChebMulti: 0 nothing, 1 final deviation, 2 traced
+    DropArgs d;                // kLaunchDrop
 };
 // What follows the launches on the stream.
 enum After : int32_t {
@@ -455,6 +466,19 @@ constexpr size_t cheb_rounds_workspace_bytes(int64_t grid, int32_t n_rows, int32
     return (trace ? partial_bytes(grid * rounds, n_rows) : 0) +
            (dev ? partial_bytes(grid, n_rows) : 0);
 }
+// dl_drop_rounds / dl_drop_rounds_plan: K rounds over failing links on LDS-resident tiles.
+// whole rounds only and the round's own checks, rounds >= 1, the round must plan path 1
+// (plan_mix), then plan_rounds' geometry for the same dl_mix_args (its refusals -- the images do
+// not fit LDS, a deviation without the doubly stochastic promise -- reworded for this entry
+// point), operands the float4 kernels reach; the workspace is dl_mix_rounds' (the deviation's
+// partial rows).  kLaunchDrop with DropArgs.  out NULL: the plan query, which needs `plan`
+// (path 3, as dl_mix_rounds_plan reports it).
+int shape_drop_rounds(const dl_drop_rounds_args *a, int n_cus, const Knobs &k, void *ws,
+                      size_t ws_bytes, dl_mix_plan *plan, Launches *out, char *err);
+// dl_link_mask: up[e] = 1 for every CSR entry that round `round` keeps (a row's first entry and
+// diagonal entries always), 0 for a failed link; host arrays, the rule of link_hash.h.
+int link_mask(const int32_t *rowptr, const int32_t *col, int32_t n_rows, uint32_t seed,
+              uint32_t round, uint32_t thr_edge, uint32_t thr_node, uint8_t *up, char *err);
 // One-pass deviation of x on the tile kernel (MIX = false): every agent of a column tile in one
 // workgroup, column mean in LDS scratch.  tile_cols > 0: x in the column-tiled layout (ldx 0).
 // DL_ERR_UNSUPPORTED without a text: the agents do not fit one tile.

@@ -457,6 +457,60 @@ def cheb_rounds(W: DeviceCsr, X, Y, Z, Zout, coef, rounds, trace=None, dev_sq=No
     return True
 
 
+def check_self_first(csr):
+    """rounds_drop folds a row's first CSR entry as its self entry (the failed links' weight
+    returns to it): ValueError unless every row of the host Csr starts with its diagonal, as
+    ``graph.from_edge_weights`` writes it."""
+    rp = np.asarray(csr.rowptr, np.int64)
+    first = np.asarray(csr.col, np.int64)[np.minimum(rp[:-1], max(len(csr.col) - 1, 0))]
+    bad = np.flatnonzero((np.diff(rp) < 1) | (first != np.arange(csr.n_rows)))
+    if bad.size:
+        raise ValueError(f"drop_rounds needs the diagonal entry first in every row of W: row "
+                         f"{int(bad[0])} does not start with it")
+
+
+def _drop_rounds_args(W, X, Y, rounds, p_edge, p_node, seed, round0, G, lr, dev_sq, dev_max, mean,
+                      tiled):
+    from .graph import drop_threshold
+    check_self_first(W.csr)
+    mix, _ = _fused_round_operands("drop_rounds", None, W, X, Y, G, lr, dev_sq, dev_max, mean,
+                                   tiled, ())
+    counter = isinstance(round0, torch.Tensor)
+    if counter and (round0.dtype != torch.int32 or round0.device != W.device or
+                    round0.numel() != 1):
+        raise ValueError("a device round counter is one int32 element on W's device")
+    return _lib.DlDropRoundsArgs(mix, int(rounds), int(seed) & 0xffffffff,
+                                 0 if counter else int(round0) & 0xffffffff,
+                                 _lib.ptr(round0) if counter else None,
+                                 drop_threshold(p_edge), drop_threshold(p_node))
+
+
+def drop_rounds_plan(W: DeviceCsr, X, Y, G=None, deviation=False, tiled=None):
+    """dl_drop_rounds_plan: the configuration ``drop_rounds`` would run for these operands, or
+    None when the pass is refused as unsupported (``dl_last_error`` has the reason)."""
+    return _fused_round_plan(
+        "dl_drop_rounds_plan",
+        lambda dev_sq, dev_max: _drop_rounds_args(W, X, Y, 1, 0.0, 0.0, 0, 0, G, 0.0, dev_sq,
+                                                  dev_max, None, tiled),
+        W, deviation)
+
+
+def drop_rounds(W: DeviceCsr, X, Y, rounds, p_edge, p_node=0.0, seed=0, round0=0, G=None, lr=0.0,
+                dev_sq=None, dev_max=None, mean=None, workspace: Workspace = None, tiled=None):
+    """``rounds`` = K gossip rounds over failing links in one HBM pass on the current stream
+    (dl_drop_rounds): Y = W_t0+K-1 ... W_t0 (X - lr G), W_t the graph's W with round t's failed
+    links removed and their weight returned to the diagonal.  A link fails with probability
+    ``p_edge``, an agent (all of its links) with ``p_node``, drawn by a hash of (seed, round,
+    link) on the device -- ``graph.link_mask`` shows a round's draw.  ``round0``: the first
+    round's index t0, an int or a one-element int32 DEVICE tensor the pass reads (never writes).
+    Y may be X itself.  ``tiled=(n_params, tile_cols)``: X, G, Y in the column-tiled layout.
+    Returns False, launching nothing, when the pass is refused as unsupported."""
+    P = tiled[0] if tiled is not None else X.shape[1]
+    args = _drop_rounds_args(W, X, Y, rounds, p_edge, p_node, seed, round0, G, lr, dev_sq,
+                             dev_max, mean, tiled)
+    return _fused_round_run("dl_drop_rounds", args, W, P, workspace)
+
+
 def _track_round_args(W, X, Y, D, Dout, G, Gold, lr, dev_sq, dev_max, mean, tiled):
     missing = ("track_round needs the tracker D, its output Dout and the gradients G, Gold"
                if D is None or Dout is None or G is None or Gold is None else None)
@@ -1827,6 +1881,37 @@ class GossipEngine:
             last = i == k - 1
             self.round(G=G if i == 0 else None, lr=lr if i == 0 else 0.0,
                        deviation=deviation and last, mean=mean if last else None)
+
+    def rounds_drop(self, k, p_edge, p_node=0.0, seed=0, round0=None, G=None, lr=0.0,
+                    deviation=False, mean=None):
+        """k rounds over failing links in one HBM pass (``drop_rounds``), X / Y ping-ponging as in
+        ``rounds``: X <- W_t0+k-1 ... W_t0 (X - lr G), every link of W down with probability
+        ``p_edge`` and every agent with ``p_node`` in each round, independently, its weight back
+        on the diagonal.  round0=None: the rounds follow on from the engine's own device counter
+        ``drop_round`` (int32, starts at 0), which an in-stream add then advances by k -- no host
+        work, so a captured step replays as the next rounds; an int: those rounds, the counter
+        untouched.  ValueError under a row order (the hash sees W's own agent ids) and for a W
+        whose rows do not start with the diagonal; RuntimeError with the refusal's text where
+        the pass does not take the graph (there is no per-round fallback)."""
+        if self.order is not None:
+            raise ValueError("rounds_drop needs the agents in agent order: build the engine with "
+                             "order=None")
+        k = int(k)
+        if k < 1:
+            return
+        own = round0 is None
+        if own and getattr(self, "drop_round", None) is None:
+            self.drop_round = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if not drop_rounds(self.W, self.X, self.Y, k, p_edge, p_node, seed,
+                           self.drop_round if own else round0, G=G, lr=lr,
+                           dev_sq=self.dev_sq if deviation else None,
+                           dev_max=self.dev_max if deviation else None, mean=mean,
+                           workspace=self.ws,
+                           tiled=(self.P, self.T) if self.layout == "tiled" else None):
+            raise RuntimeError(_lib.load().dl_last_error().decode())
+        if own:
+            self.drop_round.add_(k)
+        self.X, self.Y = self.Y, self.X
 
     def deviation(self, mean_out=None):
         if self.layout == "tiled":

@@ -416,6 +416,30 @@ def lds_slot_order_native(csr, chunks, moves=4_000_000, seed=0):
     return order.astype(np.int64), int(conf[0]), int(conf[1])
 
 
+def drop_threshold(p):
+    """The uint32 threshold of a failure probability (dlamd.h dl_drop_rounds): a draw below it is
+    down; min(floor(p 2^32), 2^32 - 1), 0 = never."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"a failure probability lies in [0, 1] (got {p})")
+    return min(int(p * 2 ** 32), 2 ** 32 - 1)
+
+
+def link_mask(csr, seed, round, p_edge, p_node=0.0):
+    """Which CSR entries of W round ``round`` of ``rounds_drop`` keeps (dl_link_mask, the rule the
+    kernel compiles): a uint8 array of nnz entries, 1 = up (a row's first entry and diagonal
+    entries always), 0 = a failed link.  Host only."""
+    import ctypes
+    from . import _lib
+    rowptr = np.ascontiguousarray(csr.rowptr, dtype=np.int32)
+    col = np.ascontiguousarray(csr.col, dtype=np.int32)
+    up = np.empty(len(col), np.uint8)
+    _lib.check(_lib.load().dl_link_mask(
+        rowptr.ctypes.data, col.ctypes.data, csr.n_rows, int(seed) & 0xffffffff,
+        int(round) & 0xffffffff, drop_threshold(p_edge), drop_threshold(p_node),
+        up.ctypes.data_as(ctypes.c_void_p)), "dl_link_mask")
+    return up
+
+
 def random_irregular_metropolis(n, lo, hi, seed):
     """Every agent on a ring (degree 2) plus random extra neighbours up to a degree drawn from
     lo..hi (no hubs: rows of lo+1 .. ~hi+3 entries), Metropolis weights, self weight first,

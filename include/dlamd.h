@@ -262,6 +262,64 @@ int dl_mix_rounds_plan_shape(int32_t n_rows, int64_t n_params, int32_t nnz,
 int dl_mix_rounds(const dl_mix_args *args, int32_t rounds, void *workspace, size_t ws_bytes,
                   dl_stream_t stream);
 
+/* `rounds` = K >= 1 gossip rounds over FAILING LINKS in one pass over HBM (no reference
+ * counterpart: the reference mixes over a fixed W): y = W_{t0+K-1} ... W_{t0} (x - lr g), the
+ * local step once, before the first round, on dl_mix_rounds' geometry (two LDS tile images of all
+ * agents).  W_t is W with round t's failed links removed and their weight returned to the
+ * diagonal.  Which links fail is a counter-based hash of (seed, round, link) computed on the
+ * device: the pass is stream-ordered, capturable and reproducible, with no host work per round.
+ * Additive: callers detect it by the symbol; DLAMD_ABI_VERSION is unchanged.
+ *   The hash (uint32 arithmetic modulo 2^32):
+ *     fmix(a): a ^= a >> 16; a *= 0x85EBCA6B; a ^= a >> 13; a *= 0xC2B2AE35; a ^= a >> 16.
+ *     u(seed, t, lo, hi) = fmix(fmix(fmix(seed + 0x9E3779B9 (t + 1)) ^ lo) ^ hi).
+ *     u(0, 0, 0, 1) = 0xfb49e243, u(5, 9, 3, 3) = 0x127b72b0.
+ *   Agent i is DOWN in round t iff u(seed, t, i, i) < thr_node.  Link {i, j}, i != j, is DOWN iff
+ *     u(seed, t, min(i, j), max(i, j)) < thr_edge or either end is down.  A threshold of 0: never.
+ *     For a probability p the threshold is min(floor(p 2^32), 2^32 - 1).  i, j are W's row and
+ *     column ids.  The mask is symmetric, so a symmetric doubly stochastic W stays doubly
+ *     stochastic up to rounding; it depends on (seed, t, i, j) alone -- not on the tile width, the
+ *     layout or how K rounds are cut into passes: rounds round0 .. round0 + K - 1 in one pass are
+ *     bit for bit the same rounds in two.
+ *   Row i of round t.  Its first CSR entry e0 is taken as its self entry (the diagonal first, as
+ *     graph.from_edge_weights writes it) and is never down; nor is any diagonal entry.
+ *     wd = w[e0], then in CSR order wd = wd + w[e] for every down entry (fp32 adds);
+ *     acc = +0.0, then in CSR order acc = acc + wd x[col[e0]] for the first entry and
+ *     acc = acc + w[e] x[col[e]] for every up entry, product and sum separate fp32 operations.
+ *     Down entries are skipped, not multiplied by zero: a down neighbour's Inf or NaN does not
+ *     reach the row.  With no link down this is dl_mix_round's fold bit for bit.
+ *   Round counter: t0 = *round0_dev when round0_dev (a device uint32, nullable) is given, else
+ *     round0.  The pass only reads it; a caller that advances it on the stream (as dl_adam_tick
+ *     advances Adam's state) replays a captured step as the next rounds.
+ *   dev_sq / dev_max / mean describe the final iterate, against the column mean of the staged
+ *     x - lr g; they need W.doubly_stochastic = 1 (and a symmetric W for the mean to be exact).
+ *   y may be x itself.  Workspace: dl_mix_workspace_bytes (deviation only), as dl_mix_rounds.
+ *   DL_ERR_INVALID: args NULL, x or y NULL, what dl_mix_round refuses, rounds < 1,
+ *     dl_drop_rounds_plan with plan NULL.
+ *   DL_ERR_UNSUPPORTED, each with its own text (no fallback: the caller would form every round's
+ *     weights itself and loop dl_mix_round): any halo, partition or lagged-deviation field; a
+ *     round that plans path 2, 4 or 5; a deviation without the doubly stochastic promise; two tile
+ *     images that do not fit LDS (or row-major n_params no multiple of a tile width that fits);
+ *     operands the float4 kernels do not reach.
+ * dl_drop_rounds_plan: DL_OK and the configuration (path 3, as dl_mix_rounds_plan), or the
+ * refusal, without touching the device. */
+typedef struct dl_drop_rounds_args {
+    dl_mix_args mix;   /* x, y, W, n_params, ld*, tile_cols, g, lr, dev_sq, dev_max, mean */
+    int32_t rounds;
+    uint32_t seed;
+    uint32_t round0;
+    const uint32_t *round0_dev;   /* nullable: device counter, read instead of round0 */
+    uint32_t thr_edge, thr_node;
+} dl_drop_rounds_args;
+int dl_drop_rounds_plan(const dl_drop_rounds_args *args, dl_mix_plan *plan);
+int dl_drop_rounds(const dl_drop_rounds_args *args, void *workspace, size_t ws_bytes,
+                   dl_stream_t stream);
+/* Which links round `round` keeps, on HOST arrays, by the rule above (the same source as the
+ * kernel's): up[e] = 1 for every CSR entry that is up -- a row's first entry and diagonal entries
+ * always -- and 0 for a failed link; one byte per entry, up[row_ptr[n_rows]] in all.  No device
+ * call.  DL_ERR_INVALID: a NULL array, n_rows <= 0, a decreasing row_ptr, a negative column. */
+int dl_link_mask(const int32_t *row_ptr, const int32_t *col, int32_t n_rows, uint32_t seed,
+                 uint32_t round, uint32_t thr_edge, uint32_t thr_node, uint8_t *up);
+
 /* `rounds` mixing rounds in one HBM pass, y = W^rounds x, with the per-round disagreement
  * trace[r] = max_a ||x_a^(r+1) - mean(x^(r+1))||_2 (device float[rounds]) for r < rounds -- what
  * Mixer.mix(times, eps) (mixer.py:18-41) evaluates after every round (_get_max_deviation,
